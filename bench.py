@@ -6,15 +6,19 @@ resident in HBM. Default workload: the configuration the north-star target is qu
 N=1e7, Q=4, c=10 (BASELINE configs[2]; it fits one MI355X). Other workloads: --workload C2|C4|C5|small.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full      # + converge phase and CPU baseline
     python bench.py --gpus N ...            # bare shell: starts its own N ranks (one process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task description): value = whole-job edge-message
-updates per second over the timed steady-state sweeps; `converge` = one converge(5e-6) from the initial
-state timed between barriers (the metric as SURVEY 8(d) words it: sweeps x E2 / wall time of the converge
-phase); roofline = algorithmic bytes per sweep / HIP-event time of the sweep kernel; cpu_baseline = the
-reference's converge() (oracle/_ref/bp_ref, or the oracle port) on a bounded sample of the same graph
-family, timed on this box's host cores.
+Prints ONE JSON line on rank 0: value = whole-job edge-message
+updates per second over the timed steady-state sweeps, ms_per_step = wall time of one timed sweep;
+roofline = algorithmic bytes per sweep / HIP-event time of the sweep kernel (from the timed sweeps).
+A plain run does only that. --full adds what takes runs of its own: `converge` = one converge(5e-6)
+from the initial state timed between barriers (the metric as SURVEY 8(d) words it: sweeps x E2 / wall
+time of the converge phase); cpu_baseline = the reference's converge() (oracle/_ref/bp_ref, or the
+oracle port) on a bounded sample of the same graph family, timed on one host core of the same machine.
+
+--dump-outputs DIR writes the state the last timed sweep left, as float64 .npy files (see dump_outputs).
 """
 import argparse
 import hashlib
@@ -57,6 +61,37 @@ WORKLOADS = {
 }
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
 CONV_CRIT = 5e-6       # the reference's default -e (main.cpp:113)
+DUMP_BYTES_PER_ARRAY = 30_000_000  # --dump-outputs: two arrays, 60 MB at most in all
+DUMP_SEED = 20240611               # fixes which rows a sampled array keeps
+
+
+def dump_rows(a, seed):
+    """a itself when it fits DUMP_BYTES_PER_ARRAY, else a fixed, seeded sample of its rows (ascending row order)"""
+    k = DUMP_BYTES_PER_ARRAY // (a.shape[1] * a.itemsize)
+    if len(a) <= k:
+        return a
+    import numpy as np
+    return a[np.sort(np.random.default_rng(seed).choice(len(a), size=k, replace=False))]
+
+
+def dump_outputs(path, runner, sharded, rank):
+    """what a caller of the timed sweeps receives, as float64 .npy under `path`:
+    marginals.npy = psi (N x Q rows, the global table on every rank count: the sweeps are partition invariant);
+    messages.npy  = the messages m_{i->j} (E2 x Q rows in the engine's edge order), one GPU only.
+    Arrays above DUMP_BYTES_PER_ARRAY keep a seeded sample of their rows, the same rows for the same workload."""
+    import numpy as np
+    if sharded:
+        arrays = {"marginals": runner.gather_marginals()}  # collective: every rank takes part
+    else:
+        psi, msg = runner.get_state()
+        arrays = {"marginals": psi, "messages": msg}
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    for i, (name, a) in enumerate(arrays.items()):
+        out = np.ascontiguousarray(dump_rows(a, DUMP_SEED + i), dtype=np.float64)
+        np.save(os.path.join(path, name + ".npy"), out)
+        print("dumped %s %s (of %d rows)" % (name, out.shape, len(a)), file=sys.stderr, flush=True)
 
 
 def source_sha():
@@ -241,7 +276,7 @@ class Watchdog:
     code 3; the launcher (self_launch above, or torchrun) then takes the other ranks down. Nothing is re-executed.
     SBMBP_PHASE_DEADLINE_S scales every deadline (default 1.0; 0 switches the watchdog off)."""
     DEADLINES = {"import": 600, "rendezvous": 300, "setup": 1800, "chunk_trials": 1800, "warmup": 300, "timed": 600,
-                 "converge": 900, "cpu_baseline": 1800, "report": 300}
+                 "dump": 600, "converge": 900, "cpu_baseline": 1800, "report": 300}
 
     def __init__(self, rank, world):
         import threading
@@ -278,12 +313,17 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="C3", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the converge phase and the CPU baseline "
+                         "(each defaults to on with --full, off without; the options below pick them one by one)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed sweeps, write the state they computed as DIR/<name>.npy (float64, <= 60 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline", default="sample", choices=["sample", "full", "none"],
-                    help="sample (default): the reference's converge() on N = 1e6 of the same family, ~10 s; full: on the "
-                         "benchmarked graph itself for 3 sweeps (SURVEY 8(d); minutes and ~20 GB at C3); none")
-    ap.add_argument("--converge", action="store_true", default=True,
-                    help="also time one converge(5e-6) from the initial state (after the timed sweeps; default on)")
+    ap.add_argument("--cpu-baseline", default=None, choices=["sample", "full", "none"],
+                    help="sample (default with --full): the reference's converge() on N = 1e6 of the same family, ~10 s; full: on "
+                         "the benchmarked graph itself for 3 sweeps (SURVEY 8(d); minutes and ~20 GB at C3); none (default without)")
+    ap.add_argument("--converge", action="store_true", default=None,
+                    help="also time one converge(5e-6) from the initial state (after the timed sweeps; default on with --full)")
     ap.add_argument("--no-converge", dest="converge", action="store_false")
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the sharded driver (RCCL collectives) even with one rank")
@@ -292,6 +332,12 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="ranks rendezvous, build their shard plans and cross-check them; no GPU work, no measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.converge is None:
+        args.converge = args.full
+    if args.cpu_baseline is None:
+        args.cpu_baseline = "sample" if args.full else "none"
 
     if "RANK" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus))
@@ -488,6 +534,10 @@ def main():
     hub_edges = int(getattr(st, "hub_edges", 0))
     bytes_per_launch = st.bytes_per_sweep - hub_edges * (24.0 * Q + 4.0) - int(st.n_hub_rows) * (8.0 * Q + 8.0)
     achieved = bytes_per_launch / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
+
+    if args.dump_outputs:  # before the converge phase, which starts again from the initial state
+        dog.enter("dump")
+        dump_outputs(args.dump_outputs, runner, sharded, rank)
 
     converge = None
     if args.converge:

@@ -394,7 +394,7 @@ def test_bench_multi_rank_line_from_a_bare_shell():
     env.pop("SBMBP_SHARD_CHUNKS", None)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "small", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "small", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline"]
     pr = subprocess.run(cmd, env=env, timeout=600, capture_output=True, text=True, cwd=ROOT)
     assert pr.returncode == 0, pr.stderr[-3000:]
     lines = [l for l in pr.stdout.splitlines() if l.startswith("{")]
@@ -408,7 +408,7 @@ def test_bench_multi_rank_line_from_a_bare_shell():
     assert d["config"]["exchange"]["transport"] == "callbacks"
     assert d["converge"]["converged"] is True and d["converge"]["overlap"] > 0.9
     assert abs(d["value"] - d["steps"] * d["config"]["E2"] / (d["ms_per_step"] * 1e-3 * d["steps"])) < 1e-6 * d["value"]
-    single = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "small", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"],
+    single = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "small", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline"],
                             env=env, timeout=600, capture_output=True, text=True, cwd=ROOT)
     assert single.returncode == 0, single.stderr[-3000:]
     s1 = json.loads([l for l in single.stdout.splitlines() if l.startswith("{")][-1])
