@@ -153,7 +153,9 @@ int sbmbp_sweep(sbmbp_engine_t *e, double damping, uint32_t n_sweeps, double *la
 
 /* compute_free_energy (belief_propagation.cpp:744-750) = -f_site + f_edge + f_nonedge;
  * parts = {f_site, f_edge, f_nonedge} (:442-504, :562-612, :675-709). The non-edge term is exact
- * (tiled N^2 kernel) for N <= the exact limit, else the moment series of DESIGN.md. */
+ * (tiled N^2 kernel) for N <= the exact limit, else the moment series of DESIGN.md section 4, whose order is
+ * capped at 4 (Q <= 8), 3 (Q = 9..16) and 2 (Q = 17..64): where the cap is reached (silently) the error is
+ * N (w/N)^(K+1) / (2(K+1)) at the cap, not 1e-12 (measured at N = 4e4, c = 10: 3e-11 at Q = 12, 1e-7 at Q = 32). */
 int sbmbp_free_energy(sbmbp_engine_t *e, double *f, double *parts /* 3 or NULL */);
 /* compute_entropy (belief_propagation.cpp:752-758); NaN for deg_corr_flag != 0 as the reference */
 int sbmbp_entropy(sbmbp_engine_t *e, double *entropy, double *parts /* 3 or NULL */);

@@ -1137,6 +1137,13 @@ double orc_bp_entropy(void *sp, int series_K, double *parts) {
     if (parts) { parts[0] = es; parts[1] = ee; parts[2] = en; }
     return (-es + ee - en);  // :752-758
 }
+// the non-edge terms alone, out = {f_nonedge, e_nonedge}: series of order series_K, or the exact O(N^2 Q^2) loops for 0.
+// (free_energy / entropy above evaluate the site terms too, and e_site costs deg^2 Q^2 per row: minutes at N = 4e4, Q = 64.)
+void orc_bp_nonedge(void *sp, int series_K, double *out) {
+    auto &s = *static_cast<bp_t *>(sp);
+    out[0] = series_K > 0 ? f_nonedge_series(s, unsigned(series_K)) : f_nonedge_exact(s);
+    out[1] = series_K > 0 ? e_nonedge_series(s, unsigned(series_K)) : e_nonedge_exact(s);
+}
 void orc_bp_em_expect(void *sp, double *na_e, double *nna_e, double *cab_e) {
     auto &s = *static_cast<bp_t *>(sp);
     em_expect(s);

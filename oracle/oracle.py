@@ -64,6 +64,7 @@ def lib():
             "orc_bp_converge_sync": (C.c_int, [C.c_void_p, C.c_double, C.c_uint, C.c_double, c_dp]),
             "orc_bp_free_energy": (C.c_double, [C.c_void_p, C.c_int, c_dp]),
             "orc_bp_entropy": (C.c_double, [C.c_void_p, C.c_int, c_dp]),
+            "orc_bp_nonedge": (None, [C.c_void_p, C.c_int, c_dp]),
             "orc_bp_em_expect": (None, [C.c_void_p, c_dp, c_dp, c_dp]),
             "orc_bp_overlap": (C.c_double, [C.c_void_p]),
             "orc_bp_learning": (C.c_int, [C.c_void_p, C.c_float, C.c_uint, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, c_dp]),
@@ -243,6 +244,12 @@ class OracleBP:
         parts = np.zeros(3)
         e = lib().orc_bp_entropy(self._h, series_K, _dp(parts))
         return e, parts
+
+    def nonedge(self, series_K=0):
+        """(f_nonedge, e_nonedge) alone: part 2 of free_energy(series_K) and entropy(series_K)"""
+        out = np.zeros(2)
+        lib().orc_bp_nonedge(self._h, series_K, _dp(out))
+        return out[0], out[1]
 
     def em_expect(self):
         na = np.zeros(self.Q)

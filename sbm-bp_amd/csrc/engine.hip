@@ -804,7 +804,8 @@ int max_series_order(uint32_t Q) {
 int choose_series_order(const sbmbp_engine *e, double wmax) {
     const int Kmax = max_series_order(e->Q);
     if (e->series_order > 0) return std::min(e->series_order, Kmax);
-    // smallest K with N (wmax/N)^(K+1) / (2(K+1)) < 1e-12  (SURVEY A.4 truncation bound)
+    // smallest K with N (wmax/N)^(K+1) / (2(K+1)) < 1e-12  (SURVEY A.4 truncation bound); where no K up to the cap meets it,
+    // the cap - silently, and then the bound of the cap is what holds (1e-7 at Q = 32, N = 4e4, c = 10)
     for (int K = 1; K <= Kmax; ++K) {
         double err = double(e->N) * std::pow(wmax / double(e->N), K + 1) / (2.0 * (K + 1));
         if (err < 1e-12) return K;
@@ -1579,6 +1580,7 @@ int sbmbp_entropy(sbmbp_engine_t *e, double *ent, double *parts) {
 int sbmbp_set_nonedge_mode(sbmbp_engine_t *e, int mode, int order) {
     device_scope dev_(e);
     if (!e || mode < 0 || mode > 2 || order < 0 || order > 4) return arg_error(__func__, __LINE__);
+    if (mode != e->nonedge_mode || order != e->series_order) e->fz.valid = false;  // the fused pass's adjacent pairs are of one form
     e->nonedge_mode = mode;
     e->series_order = order;
     return SBMBP_OK;

@@ -48,7 +48,7 @@ def _pair(S, orc, t, flag=0, conf=None, beta=1.0):
     return g, bp, ob
 
 
-@pytest.mark.parametrize("Q,dc", [(17, 0), (32, 0), (32, 1), (48, 0), (64, 0), (64, 1)])
+@pytest.mark.parametrize("Q,dc", [(17, 0), (32, 0), (32, 1), (33, 0), (40, 1), (48, 0), (49, 0), (63, 0), (64, 0), (64, 1)])
 def test_wide_sweeps_and_convergence_against_the_oracle(S, orc, Q, dc):
     t = _instance(Q, dc, seed=Q + dc)
     g, bp, ob = _pair(S, orc, t, beta=0.8 if (Q == 32 and dc == 0) else 1.0)
@@ -75,10 +75,18 @@ def test_wide_sweeps_and_convergence_against_the_oracle(S, orc, Q, dc):
         assert np.isnan(e) and np.isnan(eo)  # the reference prints -nan for deg_corr_flag != 0
     else:
         assert np.abs(np.array(ep) - eop).max() <= 1e-8 * max(1.0, np.abs(eop).max()), (ep, eop)
-        bp.set_nonedge_mode(2, 2)  # the moment series (order 2 is all the tensors of Q = 17 .. 64 allow) against the exact pairs
+        # the moment series (order 2 is all the tensors of Q = 17 .. 64 allow) against the oracle's series of the same order
+        # on the same state (tests/test_oracle_series.py pins that one to a pairwise restatement and to the exact loop)
+        bp.set_nonedge_mode(2, 2)
         f2, fp2 = bp.compute_free_energy(parts=True)
-        bound = t["N"] * (t["cab"].max() / t["N"]) ** 3 / 6.0  # SURVEY A.4 truncation bound of order 2 (1e-8 and less from N = 1e5 on)
-        assert abs(fp2[2] - fp[2]) < 4.0 * bound + 1e-9, (fp2[2], fp[2], bound)
+        e2, ep2 = bp.compute_entropy(parts=True)
+        oc = orc.OracleBP(orc.Graph.from_edges(t["pairs"], t["N"]), Q, 0)  # on the engine's state itself (1e-11 from the twin's)
+        oc.init_messages(0, None, t["tc"], orc.Rng(0))
+        oc.set_params(t["cab"], t["na"], 0.8 if (Q == 32 and dc == 0) else 1.0)
+        oc.set_state(*bp.get_state())
+        fo2, eo2 = oc.free_energy(2)[1][2], oc.entropy(2)[1][2]
+        assert abs(fp2[2] - fo2) <= 1e-11 * max(1.0, abs(fo2)), (fp2[2], fo2)
+        assert abs(ep2[2] - eo2) <= 1e-11 * max(1.0, abs(eo2)), (ep2[2], eo2)
         bp.set_nonedge_mode(0, 0)
     na1, nna1, cab1 = bp.em_expectations()
     na2, nna2, cab2 = ob.em_expect()
