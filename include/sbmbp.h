@@ -144,6 +144,27 @@ int sbmbp_get_relaxation(const sbmbp_engine_t *e, int *field_level, int *generic
  * with mode 1, incoming messages are gathered from the message array. */
 int sbmbp_set_gather_mode(sbmbp_engine_t *e, int mode);
 
+/* Sweep order (no reference counterpart in this form). order 0 = synchronous (default), 1 = coloured
+ * Gauss-Seidel: like the reference's converge (belief_propagation.cpp:394-401, 1088-1095) it never updates two neighbours
+ * at once and keeps the global field h_ current inside a sweep. Colouring: vertices in order (degree descending, index
+ * ascending) take the smallest colour no neighbour holds (self-loops ignored). Steps: classes in colour order, rows ascending
+ * inside a class, consecutive chunks of at most max(1, ceil(step_fraction * N)) rows; a step updates its rows at once, in
+ * place, from the current state and the current field, then the field is moved by the step's change of the marginals.
+ * The sweep's reported difference is the maximum over its steps of the undamped 1-step message difference.
+ * sbmbp_coloured_plan: host only, no device: the plan the engine would use. colour_in NULL = built-in greedy colouring.
+ * colour / step: N entries or NULL; step = index of the field-refresh step that updates the vertex.
+ * sbmbp_set_sweep_order: colour NULL = built-in, else N entries, validated (colour[i] != colour[j] for every edge i != j and
+ * every value < N, else SBMBP_ERR_ARG); step_fraction 0 = default 1/8, 1 = one step per class, <= 1/N = one vertex per step.
+ * sbmbp_sweep / sbmbp_converge / sbmbp_inference / sbmbp_learning follow the order set; damping is honoured. Under order 1
+ * the adaptive relaxation never engages (sbmbp_get_relaxation reports (0, -1, 1, 1)) and field_mix of sbmbp_set_schedule /
+ * sbmbp_set_learning_schedule and sbmbp_set_gather_mode are ignored; sbmbp_stats counts coloured sweeps in sweeps and
+ * edge_msg_updates, never in psi_form_sweeps, and sweep_kernel_ms covers a coloured sweep's whole launch sequence.
+ * SBMBP_ERR_UNSUPPORTED: Q > 16, shard engines (so the multi-GPU driver sbmbp_dist_* always sweeps synchronously). */
+int sbmbp_coloured_plan(const sbmbp_graph_t *g, const uint32_t *colour_in, double step_fraction, uint32_t *n_colours,
+                        uint32_t *n_steps, uint32_t *colour, uint32_t *step);
+int sbmbp_set_sweep_order(sbmbp_engine_t *e, int order, const uint32_t *colour, double step_fraction);
+int sbmbp_get_sweep_order(const sbmbp_engine_t *e, int *order, uint32_t *n_colours, uint32_t *n_steps);
+
 /* converge (belief_propagation.cpp:386-415): returns in *niter the 0-based index of the first sweep
  * whose max |delta message| < crit, or -1 after max_sweeps. damping == dumping_rate. */
 int sbmbp_converge(sbmbp_engine_t *e, double crit, uint32_t max_sweeps, double damping, int *niter,

@@ -79,6 +79,23 @@ def load_edge_list(edge_list_path, num_vertices=0):
     return Graph(h.value)
 
 
+def coloured_plan(graph, colour=None, step_fraction=0):
+    """the plan of the coloured sweep order (sbmbp.h sbmbp_coloured_plan), host only: (n_colours, n_steps, colour[N], step[N]).
+    colour=None: the built-in greedy colouring; a caller's colouring is validated (improper: SbmbpError, code -1)"""
+    lib = load_library()
+    nc, ns = C.c_uint32(0), C.c_uint32(0)
+    col = np.zeros(graph.N, dtype=np.uint32)
+    st = np.zeros(graph.N, dtype=np.uint32)
+    cin = None
+    if colour is not None:
+        cin = np.ascontiguousarray(colour, dtype=np.uint32)
+        if len(cin) != graph.N:
+            raise ValueError("colour needs N entries")
+    check(lib.sbmbp_coloured_plan(graph._h, None if cin is None else cin.ctypes.data_as(c_u32p), float(step_fraction),
+                                  C.byref(nc), C.byref(ns), col.ctypes.data_as(c_u32p), st.ctypes.data_as(c_u32p)))
+    return nc.value, ns.value, col, st
+
+
 def load_beliefs(path):
     """load_beliefs (graph_utilities.cpp:8-23): one int per line, -1 = unknown"""
     return np.loadtxt(path, dtype=np.int32, ndmin=1)
@@ -232,6 +249,24 @@ class BeliefPropagation:
     def set_learning_schedule(self, field_mix=0.3, snap=1.0):
         """field relaxation inside the EM loop's BP runs and the snap tolerance of the group-size truncation (sbmbp.h)"""
         check(self._lib.sbmbp_set_learning_schedule(self._h, field_mix, snap))
+
+    def set_sweep_order(self, order="coloured", colour=None, step_fraction=0):
+        """"jacobi" / 0: synchronous sweeps (default); "coloured" / 1: coloured Gauss-Seidel sweeps with the field refreshed
+        inside a sweep (sbmbp.h sbmbp_set_sweep_order). colour=None: built-in greedy colouring; step_fraction 0 = 1/8"""
+        code = {"jacobi": 0, "coloured": 1}.get(order, order)
+        cin = None
+        if colour is not None:
+            cin = np.ascontiguousarray(colour, dtype=np.uint32)
+            if len(cin) != self.N:
+                raise ValueError("colour needs N entries")
+        check(self._lib.sbmbp_set_sweep_order(self._h, int(code), None if cin is None else cin.ctypes.data_as(c_u32p),
+                                              float(step_fraction)))
+
+    def sweep_order(self):
+        """(order, n_colours, n_steps); order 0 = synchronous (the counts are 0), 1 = coloured"""
+        o, nc, ns = C.c_int(0), C.c_uint32(0), C.c_uint32(0)
+        check(self._lib.sbmbp_get_sweep_order(self._h, C.byref(o), C.byref(nc), C.byref(ns)))
+        return o.value, nc.value, ns.value
 
     def set_nonedge_mode(self, mode=0, series_order=0):
         check(self._lib.sbmbp_set_nonedge_mode(self._h, mode, series_order))

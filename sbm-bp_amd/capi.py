@@ -96,6 +96,9 @@ SYMBOLS = {
     "sbmbp_set_auto_relax": (C.c_int, [C.c_void_p, C.c_int]),
     "sbmbp_get_relaxation": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), c_dp, c_dp]),
     "sbmbp_set_learning_schedule": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "sbmbp_coloured_plan": (C.c_int, [C.c_void_p, c_u32p, C.c_double, c_u32p, c_u32p, c_u32p, c_u32p]),
+    "sbmbp_set_sweep_order": (C.c_int, [C.c_void_p, C.c_int, c_u32p, C.c_double]),
+    "sbmbp_get_sweep_order": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_u32p, c_u32p]),
     "sbmbp_converge": (C.c_int, [C.c_void_p, C.c_double, C.c_uint32, C.c_double, C.POINTER(C.c_int), c_dp]),
     "sbmbp_sweep": (C.c_int, [C.c_void_p, C.c_double, C.c_uint32, c_dp]),
     "sbmbp_free_energy": (C.c_int, [C.c_void_p, c_dp, c_dp]),

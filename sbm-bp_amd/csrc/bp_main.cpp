@@ -3,7 +3,8 @@
 // main.cpp:85-365, without Boost; all BP work goes through the C ABI of include/sbmbp.h.
 // Host code is C++14. Flags the reference parses but never reads (main.cpp:126-135)
 // are accepted and ignored. Extensions (default off, stdout unchanged): --precision, --device,
-// --gather, --field_mix, --check_every, --metrics_json, and --gpus N: the graph is sharded by vertex range over N GPUs of
+// --gather, --field_mix, --check_every, --metrics_json, --schedule jacobi|coloured with --step_fraction (the sweep order of
+// sbmbp_set_sweep_order; single GPU), and --gpus N: the graph is sharded by vertex range over N GPUs of
 // this node, one host thread per GPU driving the C++ multi-GPU driver (sbmbp_dist_*, RCCL over xGMI); with fewer devices
 // than ranks the ranks share devices over the in-process transport (a rehearsal, not a speed-up).
 #include <chrono>
@@ -38,7 +39,7 @@ const opt_spec OPTS[] = {
     {"pa", 0, 2}, {"cab", 0, 2}, {"if_output_marginals", 0, 0}, {"mode", 'm', 1}, {"seed", 'd', 1}, {"help", 'h', 0},
     // extensions
     {"precision", 0, 1}, {"device", 0, 1}, {"gather", 0, 1}, {"field_mix", 0, 1}, {"check_every", 0, 1}, {"metrics_json", 0, 1},
-    {"gpus", 0, 1}, {"transport", 0, 1},
+    {"gpus", 0, 1}, {"transport", 0, 1}, {"schedule", 0, 1}, {"step_fraction", 0, 1},
 };
 
 const opt_spec *find_long(const std::string &name) {
@@ -155,7 +156,10 @@ void usage(const char *argv0) {
                  "  --precision arg (=6)  --device arg (=0)  --gather auto|messages  --field_mix arg (=1)\n"
                  "  --check_every arg (=8)  --metrics_json path\n"
                  "  --gpus arg (=1)       shard the graph by vertex range over this many GPUs (one host thread each, RCCL)\n"
-                 "  --transport rccl|local  (default rccl; local = ranks may share devices, rehearsal)\n";
+                 "  --transport rccl|local  (default rccl; local = ranks may share devices, rehearsal)\n"
+                 "  --schedule jacobi|coloured (=jacobi)  sweep order: synchronous, or coloured Gauss-Seidel with the field refreshed\n"
+                 "                        inside a sweep (single GPU, up to 16 blocks)\n"
+                 "  --step_fraction arg (=0.125)  coloured order: rows updated between two field refreshes, as a fraction of N\n";
 }
 
 bool read_column(const std::string &path, std::vector<long long> &out) {  // load_beliefs/load_confs (graph_utilities.cpp:8-40)
@@ -327,6 +331,12 @@ int main(int argc, char const *argv[]) {
     std::clog << std::setprecision(int(num("precision", 6)));
 
     const int n_gpus = int(num("gpus", 1));
+    const std::string schedule = var_map.count("schedule") ? var_map.get("schedule")[0] : std::string("jacobi");
+    if (schedule != "jacobi" && schedule != "coloured") { std::clog << "bp: --schedule must be jacobi or coloured\n"; return 1; }
+    if (schedule == "coloured" && n_gpus > 1) {
+        std::clog << "bp: --schedule coloured runs on one GPU only (the multi-GPU driver sweeps synchronously); drop --gpus or use --schedule jacobi\n";
+        return 1;
+    }
     if (n_gpus > 1) {
         // ---- multi-GPU: one host thread per rank, all ranks make the same calls (include/sbmbp.h, "Multi-GPU") ----------
         const int n_dev = sbmbp_device_count();
@@ -477,6 +487,8 @@ int main(int argc, char const *argv[]) {
     if ((rc = sbmbp_set_params(eng, cab_full.data(), na.data(), beta)) != SBMBP_OK) return fail(rc);
     if ((rc = sbmbp_set_schedule(eng, num("field_mix", 1.0), unsigned(num("check_every", 8)))) != SBMBP_OK) return fail(rc);
     if (var_map.count("gather") && var_map.get("gather")[0] == "messages") sbmbp_set_gather_mode(eng, 1);
+    if (schedule == "coloured" && (rc = sbmbp_set_sweep_order(eng, 1, nullptr, num("step_fraction", 0.0))) != SBMBP_OK) return fail(rc);
+    stage("sweep order");
 
     const auto t0 = std::chrono::steady_clock::now();
     if (mode == "infer") {  // belief_propagation::inference (bp.cpp:77-99)
@@ -521,10 +533,14 @@ int main(int argc, char const *argv[]) {
         int ar_f = 0, ar_g = -1;
         double ar_mix = 1.0, ar_damp = 1.0;
         (void)sbmbp_get_relaxation(eng, &ar_f, &ar_g, &ar_mix, &ar_damp);
+        int order = 0;
+        uint32_t n_colours = 0, n_steps = 0;
+        (void)sbmbp_get_sweep_order(eng, &order, &n_colours, &n_steps);
         mj << std::setprecision(12) << "{\"sweeps\":" << st.sweeps << ",\"edge_msg_updates\":" << st.edge_msg_updates
            << ",\"marginal_gather_sweeps\":" << st.psi_form_sweeps << ",\"run_seconds\":" << secs
            << ",\"bytes_per_sweep\":" << st.bytes_per_sweep << ",\"device_bytes\":" << st.device_bytes
-           << ",\"relaxation\":[" << ar_f << "," << ar_g << "," << ar_mix << "," << ar_damp << "]}\n";
+           << ",\"relaxation\":[" << ar_f << "," << ar_g << "," << ar_mix << "," << ar_damp << "]"
+           << ",\"schedule\":\"" << (order == 1 ? "coloured" : "jacobi") << "\",\"colours\":" << n_colours << ",\"steps\":" << n_steps << "}\n";
     }
     sbmbp_destroy(eng);
     sbmbp_graph_destroy(graph);

@@ -114,6 +114,15 @@ struct sbmbp_engine {
     double learn_field_mix = 0.3, learn_snap = 1.0;  // sbmbp_set_learning_schedule
     uint32_t check_every = 1;
     int nonedge_mode = 0, series_order = 0;
+    // coloured sweep order (sbmbp_set_sweep_order; kernels.h k_sweep_step): per step a row list cut into segments, and the
+    // step's hub rows in a fragment table of their own (the scratch of the fragments, d_hub_b / pA / pE, is shared)
+    int sweep_order = 0;
+    bool cs_last = false;  // the last sweeps ran in the coloured order: the field on the device followed them step by step
+    uint32_t cs_colours = 0, cs_steps = 0, cs_max_rec = 0;
+    uint64_t cs_bytes = 0;  // HBM of the tables below
+    std::vector<uint32_t> cs_seg0, cs_hub0, cs_frag0;  // [cs_steps + 1]: first segment / hub / fragment of every step
+    uint32_t *d_cs_rows = nullptr, *d_cs_loff = nullptr, *d_cs_seg_row0 = nullptr, *d_cs_hub_row = nullptr, *d_cs_hub_rec = nullptr,
+             *d_cs_frag_hub = nullptr, *d_cs_hub_frag0 = nullptr;
     // stats
     uint64_t sweeps = 0, sweep_launches = 0;
     double sweep_ms = 0.0;
@@ -490,11 +499,195 @@ bool psi_form_allowed(const sbmbp_engine *e, double damping) {
     return !e->wide && e->gather_mode == 0 && damping == 1.0 && (!e->has_clamp || e->clamp_onehot) && e->dc != 2 && e->w_positive && e->E2 > 0;
 }
 
+void free_coloured(sbmbp_engine *e) {
+    uint32_t **ptrs[] = {&e->d_cs_rows, &e->d_cs_loff, &e->d_cs_seg_row0, &e->d_cs_hub_row, &e->d_cs_hub_rec, &e->d_cs_frag_hub, &e->d_cs_hub_frag0};
+    for (uint32_t **p : ptrs) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    e->cs_seg0.clear(); e->cs_hub0.clear(); e->cs_frag0.clear();
+    e->cs_colours = e->cs_steps = e->cs_max_rec = 0;
+    e->device_bytes -= e->cs_bytes;
+    e->cs_bytes = 0;
+}
+
+// Device tables of the coloured order from the step of every vertex (host_graph.cpp coloured_plan): rows ascending inside
+// a step, greedy segments of <= CAP edges and <= RCAP rows with the rows' edge offsets relative to their segment; rows
+// above CAP edges are the step's hubs, numbered in step order with fragments of BLOCK edges (setup_hub_frags).
+int build_coloured(sbmbp_engine *e, const std::vector<uint32_t> &step, uint32_t n_colours, uint32_t n_steps) {
+    free_coloured(e);
+    const uint32_t N = e->N, cap = uint32_t(frame_cap(e->Q)), rcap = uint32_t(frame_rcap(e->Q));
+    const std::vector<uint32_t> &rp = e->h_row_ptr;
+    std::vector<uint32_t> first(size_t(n_steps) + 1, 0u), by_step(N);
+    for (uint32_t i = 0; i < N; ++i) first[step[i] + 1]++;
+    for (uint32_t s = 0; s < n_steps; ++s) first[s + 1] += first[s];
+    { std::vector<uint32_t> pos(first.begin(), first.end() - 1); for (uint32_t i = 0; i < N; ++i) by_step[pos[step[i]]++] = i; }
+    std::vector<uint32_t> rows, loff, seg_row0(1, 0u), hub_row, hub_rec, frag_hub, hub_frag0(1, 0u);
+    rows.reserve(N); loff.reserve(size_t(N) + N / 8 + 16);
+    e->cs_seg0.assign(1, 0u); e->cs_hub0.assign(1, 0u); e->cs_frag0.assign(1, 0u);
+    uint32_t max_rec = 1;
+    for (uint32_t s = 0; s < n_steps; ++s) {
+        uint32_t nr = 0, ne = 0;
+        const uint32_t seg_first = uint32_t(seg_row0.size() - 1);
+        auto close_seg = [&]() { if (nr) { loff.push_back(ne); seg_row0.push_back(uint32_t(rows.size())); nr = 0; ne = 0; } };
+        for (uint32_t x = first[s]; x < first[s + 1]; ++x) {
+            const uint32_t i = by_step[x], d = rp[i + 1] - rp[i];
+            if (d > cap) { hub_row.push_back(i); continue; }
+            if (nr + 1 > rcap || ne + d > cap) close_seg();
+            rows.push_back(i);
+            loff.push_back(ne);
+            ++nr; ne += d;
+        }
+        close_seg();
+        const uint32_t nseg = uint32_t(seg_row0.size() - 1) - seg_first;
+        for (size_t h = e->cs_hub0.back(); h < hub_row.size(); ++h) {  // the step's records: its segments, then its hubs
+            hub_rec.push_back(nseg + uint32_t(h - e->cs_hub0.back()));
+            const uint32_t d = rp[hub_row[h] + 1] - rp[hub_row[h]];
+            for (uint32_t k = 0; k < (d + BLOCK - 1) / BLOCK; ++k) frag_hub.push_back(uint32_t(h));
+            hub_frag0.push_back(uint32_t(frag_hub.size()));
+        }
+        max_rec = std::max<uint32_t>(max_rec, nseg + uint32_t(hub_row.size() - e->cs_hub0.back()));
+        e->cs_seg0.push_back(uint32_t(seg_row0.size() - 1));
+        e->cs_hub0.push_back(uint32_t(hub_row.size()));
+        e->cs_frag0.push_back(uint32_t(frag_hub.size()));
+    }
+    if (frag_hub.size() != e->n_frag) { set_error("coloured order: fragment tables disagree"); return SBMBP_ERR_STATE; }
+    auto up = [&](uint32_t **d, const std::vector<uint32_t> &h) -> int {
+        CHK(dev_alloc(e, d, h.size()));
+        e->cs_bytes += std::max<size_t>(h.size(), 1) * 4;
+        if (!h.empty()) HIPCHK(hipMemcpyAsync(*d, h.data(), h.size() * 4, hipMemcpyHostToDevice, e->stream));
+        return SBMBP_OK;
+    };
+    CHK(up(&e->d_cs_rows, rows));
+    CHK(up(&e->d_cs_loff, loff));
+    CHK(up(&e->d_cs_seg_row0, seg_row0));
+    CHK(up(&e->d_cs_hub_row, hub_row));
+    CHK(up(&e->d_cs_hub_rec, hub_rec));
+    CHK(up(&e->d_cs_frag_hub, frag_hub));
+    CHK(up(&e->d_cs_hub_frag0, hub_frag0));
+    HIPCHK(hipStreamSynchronize(e->stream));  // the tables are locals
+    e->cs_colours = n_colours;
+    e->cs_steps = n_steps;
+    e->cs_max_rec = max_rec;
+    return SBMBP_OK;
+}
+
+// One sweep of the coloured order: per step the hub launches (if the step has hubs), k_sweep_step over the step's segments
+// and k_step_finalize, all in place on the current message buffer and marginal table.
+int launch_coloured_sweep(sbmbp_engine *e, double damp) {
+    double *M = e->d_M[e->cur], *psi = e->d_psi[e->pcur];
+    const int32_t *clamp = e->has_clamp ? e->d_clamp : nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (e->timing) {  // one pair per sweep: the step kernels AND their finalize launches (a sweep is nothing but their sequence)
+        if (e->ev_used + 2 > e->ev.size()) {
+            size_t old = e->ev.size();
+            e->ev.resize(old + 256);
+            for (size_t i = old; i < e->ev.size(); ++i) HIPCHK(hipEventCreate(&e->ev[i]));
+        }
+        e0 = e->ev[e->ev_used++];
+        e1 = e->ev[e->ev_used++];
+        HIPCHK(hipEventRecord(e0, e->stream));
+    }
+    const hub_frags hf{e->d_cs_frag_hub, e->d_cs_hub_frag0, e->d_hub_b, e->d_hub_pA, e->d_hub_pE};
+    for (uint32_t s = 0; s < e->cs_steps; ++s) {
+        const uint32_t seg0 = e->cs_seg0[s], nseg = e->cs_seg0[s + 1] - seg0, nh = e->cs_hub0[s + 1] - e->cs_hub0[s];
+        if (nh) {
+            const uint32_t f0 = e->cs_frag0[s], nf = e->cs_frag0[s + 1] - f0;
+            if (e->dc == 2) {
+                DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_frag_product_msg<QQ, true>), dim3(nf), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
+                                                    e->d_deg, M, e->d_cs_hub_row, e->d_cs_hub_rec, hf, f0, e->d_P, e->d_partials, clamp));
+            } else {
+                DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_frag_product_msg<QQ, false>), dim3(nf), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
+                                                    e->d_deg, M, e->d_cs_hub_row, e->d_cs_hub_rec, hf, f0, e->d_P, e->d_partials, clamp));
+            }
+            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_step_cavity<QQ>), dim3(nf), dim3(BLOCK), 0, e->stream, e->d_row_ptr, M, psi, e->d_cs_hub_row,
+                                                e->d_cs_hub_rec, hf, f0, e->d_P, int(e->dc != 0), damp, e->d_partials, clamp));
+        }
+        if (nseg) {
+            if (e->dc == 2) {
+                DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_step<QQ, true>), dim3(nseg), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev,
+                                                    e->d_nbr, e->d_deg, M, psi, clamp, e->d_cs_rows, e->d_cs_loff, e->d_cs_seg_row0, seg0, e->d_P, 1, damp,
+                                                    e->d_partials));
+            } else {
+                DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_step<QQ, false>), dim3(nseg), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev,
+                                                    e->d_nbr, e->d_deg, M, psi, clamp, e->d_cs_rows, e->d_cs_loff, e->d_cs_seg_row0, seg0, e->d_P, int(e->dc),
+                                                    damp, e->d_partials));
+            }
+        }
+        DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_step_finalize<QQ>), dim3(1), dim3(BLOCK), 0, e->stream, e->d_partials, nseg + nh, int(s + 1 == e->cs_steps),
+                                            e->d_P, e->d_hist, e->hist_cap));
+    }
+    if (e->timing) HIPCHK(hipEventRecord(e1, e->stream));
+    HIPCHK(hipGetLastError());
+    return SBMBP_OK;
+}
+
+// run_sweeps in the coloured order: the field sums are recomputed from the marginals at the start of every call (inside a
+// call they move by differences, step by step), the decision stays on the device (stop flag, queued no-op launches) and the
+// host reads the convergence state once per batch of check_every sweeps, one batch queued ahead.
+int run_sweeps_coloured(sbmbp_engine *e, double crit, uint32_t max_sweeps, double damping, int *niter, double *last) {
+    if (!e->have_params || !e->have_state) { set_error("set_params and init_messages/set_state must precede converge"); return SBMBP_ERR_STATE; }
+    CHK(upload_params(e, crit, false));
+    CHK(launch_field(e, 1));
+    CHK(ensure_partials(e, size_t(std::max<uint32_t>(std::max(e->n_blk, e->cs_max_rec), 1)) * (e->Q + 1)));
+    if (!e->h_cs) {
+        HIPCHK(hipHostMalloc(&e->h_cs, 2 * sizeof(conv_state), hipHostMallocDefault));
+        for (auto &ev : e->ev_cs) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    conv_state *slots = static_cast<conv_state *>(e->h_cs);
+    conv_state cs{0.0, -1, 0, 0, 0, 0, 0, 1, 0, 0, -1};
+    const uint32_t batch_max = std::max<uint32_t>(1, e->check_every);
+    uint32_t done = 0;
+    auto queue_batch = [&](int slot) -> int {
+        const uint32_t batch = std::min(batch_max, max_sweeps - done);
+        for (uint32_t b = 0; b < batch; ++b) CHK(launch_coloured_sweep(e, damping));
+        done += batch;
+        HIPCHK(hipMemcpyAsync(&slots[slot], reinterpret_cast<const char *>(e->d_P) + offsetof(dev_params, maxdiff), sizeof(conv_state),
+                              hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipEventRecord(e->ev_cs[slot], e->stream));
+        return SBMBP_OK;
+    };
+    if (max_sweeps > 0) {
+        CHK(queue_batch(0));
+        for (int k = 0;; ++k) {
+            const bool more = done < max_sweeps;
+            if (more) CHK(queue_batch((k + 1) & 1));
+            HIPCHK(hipEventSynchronize(e->ev_cs[k & 1]));
+            cs = slots[k & 1];
+            if (cs.stop || !more) {
+                if (more) {  // drain the batch queued ahead (no-ops after a stop)
+                    HIPCHK(hipEventSynchronize(e->ev_cs[(k + 1) & 1]));
+                    cs = slots[(k + 1) & 1];
+                }
+                break;
+            }
+        }
+    } else {
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    if (e->timing) CHK(collect_timing(e));
+    const uint32_t executed = uint32_t(cs.sweep_idx);
+    e->sweeps += executed;
+    if (executed > 0) {
+        e->fz.valid = false;
+        // the marginal table is no longer the product the marginal-gather form assumes: the next synchronous sweep or
+        // reduction takes the message-gather kernels, as after sbmbp_set_state
+        e->psi_consistent = false;
+        e->init_from_psi = false;
+    }
+    e->field_fresh = true;  // (of the current marginals: recomputed at the start, moved with every step since)
+    e->cs_last = true;
+    e->ar_fl = 0;
+    e->ar_gl = -1;
+    if (niter) *niter = cs.conv_iter;
+    if (last) *last = cs.maxdiff;
+    return SBMBP_OK;
+}
+
 // run sweeps until convergence (crit >= 0) or exactly max_sweeps (crit < 0: never converges). The whole decision runs on
 // the device (k_finalize: 2-step hints arm the exact criterion, the exact criterion sets the stop flag; kernels.h
 // dev_params), so the host only reads the convergence state once per batch.
 int run_sweeps(sbmbp_engine *e, double crit, uint32_t max_sweeps, double damping, int *niter, double *last) {
+    if (e->sweep_order == 1) return run_sweeps_coloured(e, crit, max_sweeps, damping, niter, last);
     if (!e->have_params || !e->have_state) { set_error("set_params and init_messages/set_state must precede converge"); return SBMBP_ERR_STATE; }
+    e->cs_last = false;
     const bool psi_ok = psi_form_allowed(e, damping);
     CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (e->Q + 1)));
     CHK(upload_params(e, crit, psi_ok));
@@ -1263,6 +1456,7 @@ void sbmbp_destroy(sbmbp_engine_t *e) {
                     e->d_clamp, e->d_M[0], e->d_M[1], e->d_psi[0], e->d_psi[1], e->d_Min, e->d_snd_ptr, e->d_snd_slot, e->d_P, e->d_partials, e->d_small, e->d_hist, e->d_mats,
                     e->d_stage, e->d_frag_hub, e->d_hub_frag0, e->d_hub_b, e->d_hub_pA, e->d_hub_pE, e->d_fold_counters, e->d_Pw};
     for (void *p : ptrs) if (p) hipFree(p);
+    free_coloured(e);
     for (auto ev : e->ev) hipEventDestroy(ev);
     if (e->h_cs) (void)hipHostFree(e->h_cs);
     for (auto ev : e->ev_cs) if (ev) hipEventDestroy(ev);
@@ -1496,7 +1690,8 @@ int sbmbp_get_field(sbmbp_engine_t *e, double *h) {
     device_scope dev_(e);
     if (!e || !h) return arg_error(__func__, __LINE__);
     NOT_SHARD(e);
-    CHK(refresh_field(e));
+    // behind coloured sweeps the field on the device is the one the sweeps maintained step by step: report THAT one
+    if (!(e->cs_last && e->field_fresh)) CHK(refresh_field(e));
     if (e->wide) {
         std::vector<double> hn(e->Q);
         HIPCHK(hipMemcpyAsync(hn.data(), reinterpret_cast<const char *>(e->d_Pw) + offsetof(dev_wide, hN), size_t(e->Q) * 8, hipMemcpyDeviceToHost, e->stream));
@@ -1536,7 +1731,7 @@ int sbmbp_get_relaxation(const sbmbp_engine_t *e, int *field_level, int *generic
     if (!e) return arg_error(__func__, __LINE__);
     if (field_level) *field_level = e->ar_fl;
     if (generic_level) *generic_level = e->ar_gl;
-    if (field_mix) *field_mix = std::min(std::min(e->field_mix, ar_field_cap(e->ar_fl)), ar_gen_mix(e->ar_gl));
+    if (field_mix) *field_mix = e->sweep_order == 1 ? 1.0 : std::min(std::min(e->field_mix, ar_field_cap(e->ar_fl)), ar_gen_mix(e->ar_gl));
     if (damping_factor) *damping_factor = ar_gen_damp(e->ar_gl);
     return SBMBP_OK;
 }
@@ -1545,6 +1740,43 @@ int sbmbp_set_gather_mode(sbmbp_engine_t *e, int mode) {
     device_scope dev_(e);
     if (!e || mode < 0 || mode > 1) return arg_error(__func__, __LINE__);
     e->gather_mode = mode;
+    return SBMBP_OK;
+}
+
+int sbmbp_coloured_plan(const sbmbp_graph_t *g, const uint32_t *colour_in, double step_fraction, uint32_t *n_colours, uint32_t *n_steps,
+                        uint32_t *colour, uint32_t *step) {
+    if (!g) return arg_error(__func__, __LINE__);
+    std::vector<uint32_t> col, st;
+    CHK(coloured_plan(g->n, g->row_ptr.data(), g->nbr.data(), colour_in, step_fraction, col, st, n_colours, n_steps));
+    if (colour) std::copy(col.begin(), col.end(), colour);
+    if (step) std::copy(st.begin(), st.end(), step);
+    return SBMBP_OK;
+}
+
+int sbmbp_set_sweep_order(sbmbp_engine_t *e, int order, const uint32_t *colour, double step_fraction) {
+    device_scope dev_(e);
+    if (!e || order < 0 || order > 1) return arg_error(__func__, __LINE__);
+    if (order == 0) { e->sweep_order = 0; return SBMBP_OK; }
+    if (e->sharded) { set_error("the coloured sweep order runs on the single engine only: a shard engine sweeps synchronously"); return SBMBP_ERR_UNSUPPORTED; }
+    if (e->wide) { set_error("the coloured sweep order is implemented up to Q = 16"); return SBMBP_ERR_UNSUPPORTED; }
+    // the engine keeps the row offsets on the host; the neighbour lists come back from the device (first use only)
+    std::vector<uint64_t> rp(e->h_row_ptr.begin(), e->h_row_ptr.end());
+    std::vector<uint32_t> nbr(e->E2);
+    if (e->E2) HIPCHK(hipMemcpyAsync(nbr.data(), e->d_nbr, e->E2 * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    std::vector<uint32_t> col, st;
+    uint32_t nc = 0, ns = 0;
+    CHK(coloured_plan(e->N, rp.data(), nbr.data(), colour, step_fraction, col, st, &nc, &ns));
+    int r = build_coloured(e, st, nc, ns);
+    if (r != SBMBP_OK) { free_coloured(e); e->sweep_order = 0; return r; }
+    e->sweep_order = 1;
+    return SBMBP_OK;
+}
+int sbmbp_get_sweep_order(const sbmbp_engine_t *e, int *order, uint32_t *n_colours, uint32_t *n_steps) {
+    if (!e) return arg_error(__func__, __LINE__);
+    if (order) *order = e->sweep_order;
+    if (n_colours) *n_colours = e->sweep_order == 1 ? e->cs_colours : 0;
+    if (n_steps) *n_steps = e->sweep_order == 1 ? e->cs_steps : 0;
     return SBMBP_OK;
 }
 
@@ -1680,6 +1912,7 @@ int sbmbp_learning(sbmbp_engine_t *e, float learning_conv_crit, uint32_t learnin
     out->free_energy = fold;
     out->total_sweeps = e->sweeps - sweeps0;
     CHK(upload_params(e, 0.0));
+    e->field_fresh = false;  // (the parameter block starts from a zero field again)
     CHK(overlap_impl(e, &out->overlap, nullptr));
     return SBMBP_OK;
 }

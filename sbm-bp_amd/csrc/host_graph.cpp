@@ -540,4 +540,62 @@ void init_state_host(uint32_t n, const uint32_t *row_ptr, uint64_t e2, uint32_t 
     pt.lap("initial state (mt19937)");
 }
 
+// Coloured sweep order (include/sbmbp.h sbmbp_coloured_plan). Colouring: vertices in order (degree
+// descending, index ascending) take the smallest colour no neighbour holds; self-loops are ignored. Steps: classes in colour
+// order, rows ascending inside a class, consecutive chunks of at most B = max(1, ceil(step_fraction N)) rows.
+int coloured_plan(uint32_t n, const uint64_t *row_ptr, const uint32_t *nbr, const uint32_t *colour_in, double step_fraction,
+                  std::vector<uint32_t> &colour, std::vector<uint32_t> &step, uint32_t *n_colours, uint32_t *n_steps) {
+    if (!(step_fraction >= 0.0)) { set_error("step_fraction must be >= 0 (0 = the default 1/8)"); return SBMBP_ERR_ARG; }
+    if (step_fraction == 0.0) step_fraction = 0.125;
+    colour.assign(n, 0u);
+    step.assign(n, 0u);
+    uint32_t nc = 0;
+    if (colour_in) {
+        for (uint32_t i = 0; i < n; ++i) {
+            if (colour_in[i] >= n) { set_error("colour values must be below the vertex count"); return SBMBP_ERR_ARG; }
+            for (uint64_t k = row_ptr[i]; k < row_ptr[i + 1]; ++k)
+                if (nbr[k] != i && colour_in[nbr[k]] == colour_in[i]) {
+                    set_error("improper colouring: vertices " + std::to_string(i) + " and " + std::to_string(nbr[k]) + " are adjacent and share colour " +
+                              std::to_string(colour_in[i]));
+                    return SBMBP_ERR_ARG;
+                }
+            colour[i] = colour_in[i];
+            nc = std::max(nc, colour_in[i] + 1);
+        }
+    } else {
+        uint64_t dmax = 0;
+        for (uint32_t i = 0; i < n; ++i) dmax = std::max<uint64_t>(dmax, row_ptr[i + 1] - row_ptr[i]);
+        // counting sort by degree, descending; ascending index inside a degree
+        std::vector<uint32_t> start(size_t(dmax) + 2, 0u), order(n);
+        for (uint32_t i = 0; i < n; ++i) start[size_t(dmax - (row_ptr[i + 1] - row_ptr[i])) + 1]++;
+        for (size_t d = 0; d + 1 < start.size(); ++d) start[d + 1] += start[d];
+        for (uint32_t i = 0; i < n; ++i) order[start[size_t(dmax - (row_ptr[i + 1] - row_ptr[i]))]++] = i;
+        const uint32_t NONE = 0xffffffffu;
+        std::vector<uint32_t> col(n, NONE), seen(size_t(dmax) + 2, NONE);  // seen[c] = last vertex that found colour c taken
+        for (uint32_t x = 0; x < n; ++x) {
+            const uint32_t i = order[x];
+            for (uint64_t k = row_ptr[i]; k < row_ptr[i + 1]; ++k) {
+                const uint32_t l = nbr[k];
+                if (l != i && col[l] != NONE) seen[col[l]] = i;  // (colours never exceed the largest degree: seen has room)
+            }
+            uint32_t c = 0;
+            while (seen[c] == i) ++c;
+            col[i] = c;
+            nc = std::max(nc, c + 1);
+        }
+        colour.swap(col);
+    }
+    const double bf = std::ceil(step_fraction * double(n));
+    const uint32_t B = bf >= double(n) ? std::max<uint32_t>(n, 1u) : std::max<uint32_t>(1u, uint32_t(bf));
+    std::vector<uint32_t> count(size_t(nc) + 1, 0u);  // rows per class -> first step of the class
+    for (uint32_t i = 0; i < n; ++i) count[colour[i]]++;
+    uint32_t ns = 0;
+    std::vector<uint32_t> first(nc, 0u);
+    for (uint32_t c = 0; c < nc; ++c) { first[c] = ns; ns += (count[c] + B - 1) / B; count[c] = 0; }
+    for (uint32_t i = 0; i < n; ++i) { const uint32_t c = colour[i]; step[i] = first[c] + count[c]++ / B; }
+    if (n_colours) *n_colours = nc;
+    if (n_steps) *n_steps = ns;
+    return SBMBP_OK;
+}
+
 }  // namespace sbmbp

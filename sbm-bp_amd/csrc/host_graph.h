@@ -47,5 +47,9 @@ struct state_sink {
 void init_state_host(uint32_t n, const uint32_t *row_ptr, uint64_t e2, uint32_t Q, uint32_t flag, const int32_t *conf,
                      uint32_t seed, double *psi, double *msg, const state_sink *sink = nullptr);
 
+// the coloured sweep order (sbmbp_coloured_plan): colour and step of every vertex; colour_in null = greedy colouring
+int coloured_plan(uint32_t n, const uint64_t *row_ptr, const uint32_t *nbr, const uint32_t *colour_in, double step_fraction,
+                  std::vector<uint32_t> &colour, std::vector<uint32_t> &step, uint32_t *n_colours, uint32_t *n_steps);
+
 }  // namespace sbmbp
 #endif

@@ -71,6 +71,7 @@ struct dev_params {
     // by every finalize launch. A row then loads its Q factors (issued before its product loop) instead of evaluating Q
     // exponentials (4 % of the sweep at Q = 8, dc 1); the entries are the very expression apply_field evaluates, bit for bit.
     double ftab[(32 + 1) * QMAX];
+    double cs_md;              // coloured sweep order: maximum difference over the steps of the current sweep so far (k_step_finalize)
 };
 constexpr int FT_D = 32;
 // With linear convergence at rate r the 2-step difference of sweep t is (1 + 1/r) times its 1-step difference d_t, and the
@@ -2655,6 +2656,318 @@ k_records_to_msgs(const double *__restrict__ rec, uint64_t n_msg, int Q, double 
     for (int q = 0; q < Q - 1; ++q) w[q] = rec[k * (Q - 1) + q];
     decode_msg_rt(w, Q, v);
     for (int q = 0; q < Q; ++q) full[k * Q + q] = v[q];
+}
+
+// ------------------------------------------------------------------------------------------------
+// Coloured Gauss-Seidel sweep order (include/sbmbp.h sbmbp_set_sweep_order). A sweep is a sequence of
+// STEPS; a step updates a list of rows that are pairwise non-adjacent (one colour class, or a chunk of one) IN PLACE from the
+// current state - one message buffer, one marginal table - and is followed by k_step_finalize, which moves the global field
+// by the step's change of the marginals before the next step starts. Step order is stream order.
+//
+// K1s: the three phases of k_sweep over a ROW LIST. The host cuts every step's list into segments of <= CAP edges and
+// <= RCAP rows (rows above CAP edges go to the fragment kernels below) and stores, per segment, the rows' edge offsets
+// relative to the segment (loff: nrows + 1 entries per segment, segment b's block at seg_row0[b] + b), so the device needs no
+// scan: edge le of the segment belongs to row r = srow[le] and sits at row_ptr[row] + (le - loff[r]).
+// M and psi are read AND written here (no __restrict__): a row gathers M[rev[k]], the out-messages of its neighbours, which
+// are in other classes and therefore not written by this launch; its own out-messages (and, for a self-loop, the slot
+// rev[k] == k) are read in phase 1 and written in phase 3, behind two workgroup barriers, and a row's edges never leave
+// its workgroup. partials[b*(Q+1) + q] = sum_rows g_i (psi_new - psi_old)[q], slot Q = max |delta message| (undamped, 1-step).
+// ------------------------------------------------------------------------------------------------
+template <int Q, bool DC2>
+__global__ void __launch_bounds__(frame_cfg<Q>::TPB) __attribute__((amdgpu_waves_per_eu(sweep_waves<Q>::N)))
+k_sweep_step(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ rev, const uint32_t *__restrict__ nbr,
+             const uint32_t *__restrict__ ndeg /* degree of every row (DC2 only) */, double *M, double *psi,
+             const int32_t *__restrict__ clamp, const uint32_t *__restrict__ rows, const uint32_t *__restrict__ loff,
+             const uint32_t *__restrict__ seg_row0, uint32_t seg_base, const dev_params *__restrict__ P, int dc, double damp,
+             double *__restrict__ partials) {
+    constexpr int EPT = frame_cfg<Q>::EPT, CAP = frame_cfg<Q>::CAP, RCAP = frame_cfg<Q>::RCAP, TPB = frame_cfg<Q>::TPB;
+    __shared__ double sb[CAP * Q];      // b_e[q] of every edge of the segment
+    __shared__ double sA[RCAP * Q];     // unnormalised marginal of every row
+    __shared__ uint32_t srp[RCAP + 1];  // edge offsets of the rows relative to the segment
+    __shared__ uint32_t sbase[RCAP];    // row_ptr of every row
+    __shared__ uint32_t sid[RCAP];      // vertex of every row
+    __shared__ uint16_t srow[CAP];      // row (within segment) of every edge
+    __shared__ uint8_t sfl[RCAP];       // 1 = clamped row
+    __shared__ double sred[frame_cfg<Q>::WAVES * (Q + 1)];
+    __shared__ int sbig;                // the segment holds a row above BIG_ROW edges
+
+    const int tid = threadIdx.x;
+    if (P->stop) return;  // stopped run: uniform exit before any barrier
+    const uint32_t b = seg_base + blockIdx.x;
+    const uint32_t l0 = seg_row0[b];
+    const int nrows = int(seg_row0[b + 1] - l0);
+    const uint32_t *lo = loff + size_t(l0) + b;
+    const int ne = (nrows >= 0 && nrows <= RCAP) ? int(lo[nrows]) : CAP + 1;
+    if (nrows > RCAP || ne > CAP) return;  // never with the host's tables (uniform): nothing is indexed beyond the LDS arrays
+    if (tid == 0) sbig = 0;
+    for (int r = tid; r <= nrows; r += TPB) srp[r] = lo[r];
+    for (int r = tid; r < nrows; r += TPB) {
+        const uint32_t i = rows[l0 + r];
+        sid[r] = i;
+        sbase[r] = row_ptr[i];
+        sfl[r] = (clamp != nullptr && clamp[i] != -1) ? 1 : 0;
+    }
+    __syncthreads();
+    for (int r = tid; r < nrows; r += TPB) {
+        const int es = int(srp[r]), ee = int(srp[r + 1]);
+        if (ee - es > BIG_ROW) sbig = 1;
+        for (int e = es; e < ee; ++e) srow[e] = uint16_t(r);
+    }
+    __syncthreads();
+
+    // ---- phase 1: lane per directed edge: own old message kept, incoming message gathered, b = W^T m -> LDS
+    double mo[EPT][Q];
+    uint32_t kk[EPT];
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        const int le = j * TPB + tid;
+        kk[j] = 0u;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) mo[j][q] = 0.0;
+        if (le < ne) {
+            const int r = srow[le];
+            kk[j] = sbase[r] + (uint32_t(le) - srp[r]);
+            const uint32_t rk = rev[kk[j]];
+            double mi[Q];
+            load_msg<Q>(M, size_t(kk[j]), mo[j]);
+            load_msg<Q>(M, size_t(rk), mi);
+            double didl = 0.0;
+            if (DC2) didl = double(srp[r + 1] - srp[r]) * double(ndeg[nbr[kk[j]]]);
+            double bv[Q];
+            edge_field<Q, DC2>(P, mi, didl, bv);
+            store_vec<Q>(&sb[le * Q], bv);
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 2: lane per row (a wave per row above BIG_ROW edges), as k_sweep; the marginal is replaced in place and
+    //      its change enters the field sums
+    double Sacc[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) Sacc[q] = 0.0;
+    auto finish_row = [&](int r, double di, double (&A)[Q], const int *ae, const double *ft = nullptr) {
+        double pv[Q], pold[Q];
+        double tot;
+        if (ae) {
+            int x[Q];
+#pragma unroll
+            for (int q = 0; q < Q; ++q) x[q] = ae[q];
+            tot = apply_field_x<Q>(P, dc, di, A, x);
+        } else {
+            tot = apply_field<Q>(P, dc, di, A, ft);
+        }
+        store_vec<Q>(&sA[r * Q], A);
+        const double inv = 1.0 / tot;
+        const double gi = dc ? di : 1.0;
+        double *prow = psi + size_t(sid[r]) * Q;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) pold[q] = prow[q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) { pv[q] = A[q] * inv; Sacc[q] += gi * (pv[q] - pold[q]); }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) prow[q] = pv[q];
+    };
+    for (int r = tid; r < nrows; r += TPB) {
+        const int es = int(srp[r]), ee = int(srp[r + 1]);
+        if (!sfl[r] && ee - es <= BIG_ROW) {  // (clamped rows keep marginal and out-messages, bp.cpp:1115-1124)
+            double A[Q], ft[Q];
+            const bool tab = dc != 0 && ee - es <= FT_D;
+            if (tab) load_vec<Q>(P->ftab + size_t(ee - es) * QMAX, ft);
+#pragma unroll
+            for (int q = 0; q < Q; ++q) A[q] = 1.0;
+            for (int e = es; e < ee; ++e) {
+                double bv[Q];
+                load_vec<Q>(&sb[e * Q], bv);
+#pragma unroll
+                for (int q = 0; q < Q; ++q) A[q] *= bv[q];
+                rescale_pow2<Q>(A);
+            }
+            finish_row(r, double(ee - es), A, nullptr, tab ? ft : nullptr);
+        }
+    }
+    if (sbig)  // uniform: written before the barrier that precedes phase 1
+    for (int r = tid >> 6; r < nrows; r += frame_cfg<Q>::WAVES) {  // wave-uniform row index
+        const int es = int(srp[r]), ee = int(srp[r + 1]);
+        if (ee - es > BIG_ROW && !sfl[r]) {
+            double A[Q];
+            int ae[Q];
+            row_product_wave<Q>(sb, es, ee, A, ae);
+            if ((tid & 63) == 0) finish_row(r, double(ee - es), A, ae);
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 3: lane per directed edge: cavity, normalise, damp, store over the own old message
+    double md = 0.0;
+#pragma unroll
+    for (int j = 0; j < EPT; ++j) {
+        const int le = j * TPB + tid;
+        if (le < ne) {
+            const int r = srow[le];
+            if (sfl[r]) continue;
+            double A[Q], bv[Q], cav[Q], out[Q];
+            load_vec<Q>(&sA[r * Q], A);
+            load_vec<Q>(&sb[le * Q], bv);
+            bool ok = true;
+            double tot = 0.0;
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                cav[q] = A[q] / bv[q];
+                ok = ok && (bv[q] > 0.0) && (cav[q] <= 1.7e308);
+                tot += cav[q];
+            }
+            if (!ok) {  // exact cavity product when a division is unusable (b == 0 or overflow)
+                const int es = int(srp[r]), ee = int(srp[r + 1]);
+                int ce[Q];
+#pragma unroll
+                for (int q = 0; q < Q; ++q) { cav[q] = 1.0; ce[q] = 0; }
+                for (int e = es; e < ee; ++e) {
+                    if (e == le) continue;
+#pragma unroll
+                    for (int q = 0; q < Q; ++q) cav[q] *= sb[e * Q + q];
+                    x_norm<Q>(cav, ce);
+                }
+                tot = apply_field_x<Q>(P, dc, double(ee - es), cav, ce);
+            }
+            const double inv = 1.0 / tot;
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const double nv = cav[q] * inv;
+                out[q] = damp * nv + (1.0 - damp) * mo[j][q];
+                md = nanmax(md, fabs(mo[j][q] - nv));  // against the undamped value (bp.cpp:1059-1063)
+            }
+            store_msg<Q>(M, size_t(kk[j]), out);
+        }
+    }
+    block_reduce_store<Q, frame_cfg<Q>::WAVES>(Sacc, md, sred, partials + size_t(blockIdx.x) * (Q + 1));
+}
+
+// K1hs: second launch of a step's hub rows (the first is k_hub_frag_product_msg over the step-ordered fragment table, which
+// only reads M): k_hub_frag_cavity_msg in place. M and psi are read and written (no __restrict__): a lane reads its own slot
+// before it writes it, lane 0 of the row's first fragment reads the old marginal before it writes the new one, and nobody
+// else touches either. rec[0..Q) = g_i (psi_new - psi_old); the maximum difference meets in rec[Q] as in the other kernels.
+template <int Q>
+__global__ void __launch_bounds__(BLOCK)
+k_hub_step_cavity(const uint32_t *__restrict__ row_ptr, double *M, double *psi, const uint32_t *__restrict__ hub_row,
+                  const uint32_t *__restrict__ hub_rec, hub_frags hf, uint32_t frag_first, const dev_params *__restrict__ P, int dc,
+                  double damp, double *__restrict__ partials, const int32_t *__restrict__ clamp) {
+    if (P->stop) return;
+    __shared__ double sAw[(BLOCK / 64) * Q];
+    __shared__ int sEw[(BLOCK / 64) * Q];
+    __shared__ double smd[BLOCK / 64];
+    const int tid = threadIdx.x;
+    const uint32_t f = frag_first + blockIdx.x, h = hf.frag_hub[f], f0 = hf.hub_frag0[h], nf = hf.hub_frag0[h + 1] - f0;
+    const uint32_t i = hub_row[h];
+    const uint32_t e0 = row_ptr[i], d = row_ptr[i + 1] - e0;
+    const double di = double(d);
+    const uint32_t le = (f - f0) * BLOCK + tid;
+    double *rec = partials + size_t(hub_rec[h]) * (Q + 1);
+    if (clamp != nullptr && clamp[i] != -1) {  // clamped hub (uniform): nothing moves
+        if (f == f0 && tid == 0) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q) rec[q] = 0.0;
+        }
+        return;
+    }
+    double A[Q];
+    int ae[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) { A[q] = 1.0; ae[q] = 0; }
+    for (uint32_t x = tid; x < nf; x += BLOCK) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) { A[q] *= hf.pA[size_t(f0 + x) * Q + q]; ae[q] += hf.pE[size_t(f0 + x) * Q + q]; }
+        x_norm<Q>(A, ae);
+    }
+    block_product_shfl<Q, BLOCK / 64>(A, ae, sAw, sEw);
+    const double tot = apply_field_x<Q>(P, dc, di, A, ae);
+    const double inv = 1.0 / tot;
+    if (f == f0 && tid == 0) {
+        double pv[Q], pold[Q];
+        double *prow = psi + size_t(i) * Q;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) pold[q] = prow[q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) { pv[q] = A[q] * inv; rec[q] = (dc ? di : 1.0) * (pv[q] - pold[q]); }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) prow[q] = pv[q];
+    }
+    double md = 0.0;
+    if (le < d) {
+        double bv[Q], mo[Q], out[Q], cav[Q];
+        load_vec<Q>(hf.b + (size_t(f) * BLOCK + tid) * Q, bv);
+        load_msg<Q>(M, size_t(e0 + le), mo);
+        double ct = 0.0;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) { cav[q] = (bv[q] > 0.0) ? A[q] / bv[q] : 0.0; ct += cav[q]; }
+        const double ci = 1.0 / ct;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const double nv = cav[q] * ci;
+            out[q] = damp * nv + (1.0 - damp) * mo[q];
+            md = nanmax(md, fabs(mo[q] - nv));
+        }
+        store_msg<Q>(M, size_t(e0 + le), out);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) md = nanmax(md, __shfl_xor(md, o, 64));
+    if ((tid & 63) == 0) smd[tid >> 6] = md;
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 1; w < BLOCK / 64; ++w) md = nanmax(md, smd[w]);
+        atomicMax(reinterpret_cast<unsigned long long *>(rec + Q), (unsigned long long)__double_as_longlong(fabs(md)));
+    }
+}
+
+// K2s (one workgroup, after every step): fixed-order fold of the step's records, S <- S + sum_step g_i (psi_new - psi_old),
+// h / eta exp(-beta h/N) / ftab rewritten for the next step, the sweep's maximum difference carried in cs_md; behind the last
+// step of a sweep the convergence bookkeeping of finalize_update (maxdiff, conv_iter, sweep_idx, stop). No relaxation of any
+// kind here: field_mix and the adaptive ladder belong to the synchronous order. Loads before stores, as in finalize_update.
+template <int Q>
+__device__ __forceinline__ void step_update(dev_params *__restrict__ P, const double *sums /* [Q] then the max */, int last_step,
+                                            double *__restrict__ diff_hist, uint32_t hist_cap, double *s_hN) {
+    double cab[Q * Q], eta[Q], S[Q];
+#pragma unroll
+    for (int a = 0; a < Q * Q; ++a) cab[a] = P->cab[a];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) { eta[q] = P->eta[q]; S[q] = P->S[q] + sums[q]; }
+    const double invN = P->invN, beta = P->beta, crit = P->crit;
+    const double md = nanmax(P->cs_md, sums[Q]);
+    const int conv_iter = P->conv_iter, it = P->sweep_idx;
+    double hN[Q], etaF[Q];
+#pragma unroll
+    for (int q1 = 0; q1 < Q; ++q1) {  // h[q1] = sum_q2 cab[q2][q1] S[q2]   (bp.cpp:341-355)
+        double h = 0.0;
+#pragma unroll
+        for (int q2 = 0; q2 < Q; ++q2) h += cab[q2 * Q + q1] * S[q2];
+        hN[q1] = h * invN;
+        etaF[q1] = eta[q1] * exp(-beta * hN[q1]);
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) { P->S[q] = S[q]; P->hN[q] = hN[q]; P->etaF[q] = etaF[q]; s_hN[q] = hN[q]; }
+    if (!last_step) { P->cs_md = md; return; }
+    P->cs_md = 0.0;
+    P->maxdiff = md;
+    if (diff_hist != nullptr && uint32_t(it) < hist_cap) diff_hist[it] = md;
+    P->last_exact = 1;
+    if (md < crit && conv_iter < 0) {  // (a NaN difference never passes)
+        P->conv_iter = it;
+        P->stop = 1;
+    }
+    P->sweep_idx = it + 1;
+}
+template <int Q>
+__global__ void __launch_bounds__(BLOCK)
+k_step_finalize(const double *__restrict__ partials, uint32_t n_rec, int last_step, dev_params *__restrict__ P,
+                double *__restrict__ diff_hist, uint32_t hist_cap) {
+    if (P->stop) return;
+    __shared__ double sacc[(BLOCK / 64) * (Q + 1)];
+    __shared__ double sout[Q + 1];
+    __shared__ double s_hN[Q];
+    fold_rows<Q, false>(partials, 0, n_rec, sacc, sout);
+    if (threadIdx.x == 0) step_update<Q>(P, sout, last_step, diff_hist, hist_cap, s_hN);
+    __syncthreads();
+    field_table<Q>(P, s_hN);
 }
 
 }  // namespace sbmbp

@@ -17,7 +17,7 @@ from concurrent.futures import FIRST_EXCEPTION, ThreadPoolExecutor, wait
 import numpy as np
 
 from sbm_bp_amd.capi import (COMM_ID_BYTES, CommCallbacks, DistInfo, InferResult, LearnResult, Stats, c_dp, c_i32p, c_u32p, c_u64p,
-                             check, load_library)
+                             SbmbpError, check, load_library)
 
 
 def _dp(a):
@@ -212,6 +212,11 @@ class ShardedBP:
     def set_gather_mode(self, mode=0):
         check(self._lib.sbmbp_dist_set_gather_mode(self._h, mode))
 
+    def set_sweep_order(self, order="jacobi", colour=None, step_fraction=0):
+        """the multi-GPU driver sweeps synchronously: anything but "jacobi" / 0 is refused (sbmbp.h sbmbp_set_sweep_order)"""
+        if order not in ("jacobi", 0):
+            raise SbmbpError(-6, "unsupported", "the coloured sweep order runs on the single engine only: the multi-GPU driver sweeps synchronously")
+
     def set_auto_relax(self, on=True):
         check(self._lib.sbmbp_dist_set_auto_relax(self._h, int(on)))
 
@@ -371,6 +376,9 @@ class LocalShards:
 
     def set_gather_mode(self, mode=0):
         self._all(lambda sh: sh.set_gather_mode(mode))
+
+    def set_sweep_order(self, order="jacobi", colour=None, step_fraction=0):
+        self._all(lambda sh: sh.set_sweep_order(order, colour, step_fraction))
 
     def set_auto_relax(self, on=True):
         self._all(lambda sh: sh.set_auto_relax(on))
