@@ -236,6 +236,62 @@ int sbmbp_reset_stats(sbmbp_engine_t *e);
 int sbmbp_set_timing(sbmbp_engine_t *e, int on);
 
 /* ---------------------------------------------------------------------------------------------
+ * Replica batches: R independent BP runs over ONE graph on one GPU (csrc/kernels_batch.h). No reference counterpart: the
+ * reference runs one state per process. BP on a block model is multistable, so it is run from several starts and the fixed
+ * point of lowest free energy is kept; a batch uploads the CSR once and advances all replicas with one launch sequence per
+ * sweep. Every replica has its own initial state, its own (cab, na, beta) and its own convergence and adaptive-relaxation
+ * state: replica r stops at its own sweep and keeps the state of that sweep, exactly as a single engine with
+ * sbmbp_set_gather_mode(e, 1) started from the same state would.
+ * Layout in HBM (replica-major): messages [2][R][E2][Q-1], marginals [2][R][N][Q], parameter blocks [R], sweep records
+ * [R][n_segments][Q+1].
+ * Supported: Q = 2 .. 16, deg_corr_flag 0 / 1 / 2, zeros in cab, clamped rows, rows of any degree, damping, beta; the
+ * synchronous sweep order in the message-gather form. Refused with SBMBP_ERR_UNSUPPORTED: Q > 16. A batch has no shard
+ * form, no coloured sweep order and no marginal-gather form (there are no entry points that would select them).
+ * SBMBP_ERR_ARG: n_replicas = 0 or above 65535 (the replica is the second grid dimension), Q < 2, a replica index >= R.
+ * SBMBP_ERR_NOMEM: R (2 E2 (Q-1) + 2 N Q) 8 bytes of state do not fit the free HBM. Argument errors are reported before
+ * any device work; without a GPU the call returns SBMBP_ERR_NODEVICE as sbmbp_create does.
+ * The calls mirror the single-engine ones (same reference citations); arrays over replicas have R leading entries.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct sbmbp_batch sbmbp_batch_t;
+int sbmbp_batch_create(sbmbp_batch_t **out, const sbmbp_graph_t *g, uint32_t Q, uint32_t deg_corr_flag, uint32_t n_replicas, int device);
+void sbmbp_batch_destroy(sbmbp_batch_t *b);
+uint32_t sbmbp_batch_num_replicas(const sbmbp_batch_t *b);
+/* replica r is bit for bit what sbmbp_init_messages produces with seeds[r]; conf / true_conf / conditional are common */
+int sbmbp_batch_init_messages(sbmbp_batch_t *b, uint32_t flag, const int32_t *conf, const uint32_t *true_conf,
+                              const uint32_t *seeds /* R */, int conditional);
+int sbmbp_batch_init_messages_device(sbmbp_batch_t *b, const uint64_t *seeds /* R */, const uint32_t *true_conf);
+/* replica = -1: all replicas */
+int sbmbp_batch_set_params(sbmbp_batch_t *b, int replica, const double *cab, const uint32_t *na, double beta);
+int sbmbp_batch_get_params(sbmbp_batch_t *b, uint32_t replica, double *cab, uint32_t *na, double *beta /* each may be NULL */);
+int sbmbp_batch_set_state(sbmbp_batch_t *b, uint32_t replica, const double *psi, const double *msg_out);
+int sbmbp_batch_get_state(sbmbp_batch_t *b, uint32_t replica, double *psi, double *msg_out);
+int sbmbp_batch_get_field(sbmbp_batch_t *b, uint32_t replica, double *h /* Q */);
+int sbmbp_batch_get_relaxation(const sbmbp_batch_t *b, uint32_t replica, int *field_level, int *generic_level, double *field_mix,
+                               double *damping_factor);
+/* common to all replicas */
+int sbmbp_batch_set_schedule(sbmbp_batch_t *b, double field_mix, uint32_t check_every);
+int sbmbp_batch_set_auto_relax(sbmbp_batch_t *b, int on);
+int sbmbp_batch_set_nonedge_mode(sbmbp_batch_t *b, int nonedge_mode, int series_order);
+/* exactly n_sweeps sweeps of every replica (never relaxed); last_maxdiff: R entries or NULL */
+int sbmbp_batch_sweep(sbmbp_batch_t *b, double damping, uint32_t n_sweeps, double *last_maxdiff);
+/* niter[r] / last_maxdiff[r]: sbmbp_converge's meaning for replica r alone. The call ends when every replica has stopped
+ * or after max_sweeps; the host reads the R convergence states every check_every sweeps (one copy). */
+int sbmbp_batch_converge(sbmbp_batch_t *b, double crit, uint32_t max_sweeps, double damping, int *niter /* R */,
+                         double *last_maxdiff /* R */);
+/* per replica, through the single engine's reduction kernels and host code on replica r's buffers */
+int sbmbp_batch_free_energy(sbmbp_batch_t *b, double *f /* R */, double *parts /* 3 R or NULL */);
+int sbmbp_batch_entropy(sbmbp_batch_t *b, double *entropy /* R */, double *parts /* 3 R or NULL */);
+int sbmbp_batch_overlap(sbmbp_batch_t *b, double *overlap /* R */);
+int sbmbp_batch_em_expectations(sbmbp_batch_t *b, uint32_t replica, double *na_expect, double *nna_expect, double *cab_expect);
+/* inference of every replica; *best (may be NULL) = the replica of lowest free energy among those with niter >= 0, among
+ * all when none converged; a NaN free energy is never best; ties go to the lowest index */
+int sbmbp_batch_inference(sbmbp_batch_t *b, float conv_crit, uint32_t time_conv, float dumping_rate, sbmbp_infer_result *out /* R */,
+                          uint32_t *best);
+/* sweeps = sum over replicas of the sweeps actually executed, edge_msg_updates = sweeps * E2, psi_form_sweeps = 0;
+ * bytes_per_sweep is one replica's; the kernel-time fields are 0 */
+int sbmbp_batch_get_stats(sbmbp_batch_t *b, sbmbp_stats *out);
+
+/* ---------------------------------------------------------------------------------------------
  * Vertex-range sharding: the per-shard STEPS (one engine per GPU). No reference counterpart: the
  * reference is single-process. A shard owns a contiguous range of rows, their out-messages and
  * marginals; the marginals of remote neighbours ("halo") live behind the owned rows in the same

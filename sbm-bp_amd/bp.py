@@ -383,6 +383,160 @@ class bp_conditional(BeliefPropagation):
     conditional = True
 
 
+class ReplicaBatch:
+    """R independent BP runs over one graph in one launch sequence per sweep (sbmbp.h: sbmbp_batch_*). Every replica has its
+    own initial state, its own (cab, na, beta) and its own convergence and relaxation state; arrays over replicas have
+    shape [R, ...]. Q = 2 .. 16, synchronous sweeps in the message-gather form."""
+
+    def __init__(self, graph, Q, deg_corr_flag=0, n_replicas=1, device=-1):
+        self._lib = load_library()
+        self._h = None
+        h = C.c_void_p()
+        check(self._lib.sbmbp_batch_create(C.byref(h), graph._h, int(Q), int(deg_corr_flag), int(n_replicas), int(device)))
+        self._h = h
+        self._graph = graph  # (the batch copies what it needs; kept so that the caller's graph outlives the views it handed out)
+        self.R, self.Q, self.N, self.E2 = int(n_replicas), int(Q), graph.N, graph.E2
+
+    def close(self):
+        if self._h:
+            self._lib.sbmbp_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # the batch holds no pointer into the graph: the order in which the two are collected does not matter
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _replica(self, r):
+        r = int(r)
+        if r < 0:
+            raise ValueError("replica index must be >= 0")
+        return r
+
+    # -- state and parameters ---------------------------------------------------------------
+    def init_messages(self, bp_messages_init_flag, conf, true_conf, seeds, conditional=True):
+        """replica r starts bit for bit as BeliefPropagation.init_messages(..., seeds[r]) does"""
+        tc = np.ascontiguousarray(true_conf, dtype=np.uint32)
+        if len(tc) != self.N:
+            raise ValueError("true_conf needs N entries")
+        cf = None
+        if conf is not None and len(conf):
+            cf = np.ascontiguousarray(conf, dtype=np.int32)
+            if len(cf) != self.N:
+                raise ValueError("conf needs N entries (-1 = unknown)")
+        sd = np.ascontiguousarray(seeds, dtype=np.uint32)
+        if len(sd) != self.R:
+            raise ValueError("seeds needs one entry per replica")
+        check(self._lib.sbmbp_batch_init_messages(self._h, bp_messages_init_flag, None if cf is None else cf.ctypes.data_as(c_i32p),
+                                                  tc.ctypes.data_as(c_u32p), sd.ctypes.data_as(c_u32p), int(conditional)))
+
+    def init_messages_device(self, true_conf, seeds):
+        tc = np.ascontiguousarray(true_conf, dtype=np.uint32)
+        sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+        if len(sd) != self.R:
+            raise ValueError("seeds needs one entry per replica")
+        check(self._lib.sbmbp_batch_init_messages_device(self._h, sd.ctypes.data_as(c_u64p), tc.ctypes.data_as(c_u32p)))
+
+    def set_params(self, state, beta=1.0, replica=-1):
+        """replica = -1: all replicas"""
+        cab = np.ascontiguousarray(state.cab, dtype=np.float64)
+        na = np.ascontiguousarray(state.na, dtype=np.uint32)
+        check(self._lib.sbmbp_batch_set_params(self._h, int(replica), _dp(cab), na.ctypes.data_as(c_u32p), float(beta)))
+
+    def get_params(self, replica):
+        cab = np.zeros((self.Q, self.Q))
+        na = np.zeros(self.Q, dtype=np.uint32)
+        beta = C.c_double(0.0)
+        check(self._lib.sbmbp_batch_get_params(self._h, self._replica(replica), _dp(cab), na.ctypes.data_as(c_u32p), C.byref(beta)))
+        return cab, na, beta.value
+
+    def get_state(self, replica, psi=True, msg=True):
+        p = np.zeros((self.N, self.Q)) if psi else None
+        m = np.zeros((self.E2, self.Q)) if msg else None
+        check(self._lib.sbmbp_batch_get_state(self._h, self._replica(replica), _dp(p), _dp(m)))
+        return p, m
+
+    def set_state(self, replica, psi, msg_out):
+        p = None if psi is None else np.ascontiguousarray(psi, dtype=np.float64)
+        m = None if msg_out is None else np.ascontiguousarray(msg_out, dtype=np.float64)
+        check(self._lib.sbmbp_batch_set_state(self._h, self._replica(replica), _dp(p), _dp(m)))
+
+    def h(self, replica):
+        h = np.zeros(self.Q)
+        check(self._lib.sbmbp_batch_get_field(self._h, self._replica(replica), _dp(h)))
+        return h
+
+    def relaxation(self, replica):
+        """(field level, generic level, field_mix, damping factor) replica's last converge call ended on"""
+        fl, gl, mix, dmp = C.c_int(0), C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        check(self._lib.sbmbp_batch_get_relaxation(self._h, self._replica(replica), C.byref(fl), C.byref(gl), C.byref(mix), C.byref(dmp)))
+        return fl.value, gl.value, mix.value, dmp.value
+
+    def set_schedule(self, field_mix=1.0, check_every=1):
+        check(self._lib.sbmbp_batch_set_schedule(self._h, field_mix, check_every))
+
+    def set_auto_relax(self, on=True):
+        check(self._lib.sbmbp_batch_set_auto_relax(self._h, int(on)))
+
+    def set_nonedge_mode(self, mode=0, series_order=0):
+        check(self._lib.sbmbp_batch_set_nonedge_mode(self._h, mode, series_order))
+
+    # -- hot path ---------------------------------------------------------------------------
+    def sweep(self, n_sweeps=1, dumping_rate=1.0):
+        """exactly n_sweeps sweeps of every replica; returns the last max|delta message| of each, shape [R]"""
+        last = np.zeros(self.R)
+        check(self._lib.sbmbp_batch_sweep(self._h, dumping_rate, n_sweeps, _dp(last)))
+        return last
+
+    def converge(self, conv_crit, time_conv, dumping_rate):
+        """(niter [R], last max|delta| [R]): each replica stops at its own sweep and keeps the state of that sweep"""
+        niter = np.zeros(self.R, dtype=np.int32)
+        last = np.zeros(self.R)
+        check(self._lib.sbmbp_batch_converge(self._h, conv_crit, time_conv, dumping_rate, niter.ctypes.data_as(C.POINTER(C.c_int)), _dp(last)))
+        return niter, last
+
+    def compute_free_energy(self, parts=False):
+        f = np.zeros(self.R)
+        p = np.zeros((self.R, 3))
+        check(self._lib.sbmbp_batch_free_energy(self._h, _dp(f), _dp(p)))
+        return (f, p) if parts else f
+
+    def compute_entropy(self, parts=False):
+        e = np.zeros(self.R)
+        p = np.zeros((self.R, 3))
+        check(self._lib.sbmbp_batch_entropy(self._h, _dp(e), _dp(p)))
+        return (e, p) if parts else e
+
+    def compute_overlap(self):
+        ov = np.zeros(self.R)
+        check(self._lib.sbmbp_batch_overlap(self._h, _dp(ov)))
+        return ov
+
+    def em_expectations(self, replica, cab=True):
+        na, nna, cabe = np.zeros(self.Q), np.zeros(self.Q), np.zeros((self.Q, self.Q))
+        check(self._lib.sbmbp_batch_em_expectations(self._h, self._replica(replica), _dp(na), _dp(nna), _dp(cabe) if cab else None))
+        return na, nna, cabe
+
+    def inference(self, conv_crit, time_conv, dumping_rate):
+        """inference of every replica: (list of R result structs, index of the replica of lowest free energy)"""
+        res = (InferResult * self.R)()
+        best = C.c_uint32(0)
+        check(self._lib.sbmbp_batch_inference(self._h, conv_crit, time_conv, dumping_rate, res, C.byref(best)))
+        return list(res), best.value
+
+    def stats(self):
+        s = Stats()
+        check(self._lib.sbmbp_batch_get_stats(self._h, C.byref(s)))
+        return s
+
+
 def format_infer_line(res):
     """the stdout line of belief_propagation.cpp:88 at the default 6 significant digits"""
     def g(x):

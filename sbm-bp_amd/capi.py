@@ -112,6 +112,29 @@ SYMBOLS = {
     "sbmbp_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "sbmbp_reset_stats": (C.c_int, [C.c_void_p]),
     "sbmbp_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
+    # replica batches (sbm_bp_amd.bp.ReplicaBatch)
+    "sbmbp_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]),
+    "sbmbp_batch_destroy": (None, [C.c_void_p]),
+    "sbmbp_batch_num_replicas": (C.c_uint32, [C.c_void_p]),
+    "sbmbp_batch_init_messages": (C.c_int, [C.c_void_p, C.c_uint32, c_i32p, c_u32p, c_u32p, C.c_int]),
+    "sbmbp_batch_init_messages_device": (C.c_int, [C.c_void_p, c_u64p, c_u32p]),
+    "sbmbp_batch_set_params": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_u32p, C.c_double]),
+    "sbmbp_batch_get_params": (C.c_int, [C.c_void_p, C.c_uint32, c_dp, c_u32p, c_dp]),
+    "sbmbp_batch_set_state": (C.c_int, [C.c_void_p, C.c_uint32, c_dp, c_dp]),
+    "sbmbp_batch_get_state": (C.c_int, [C.c_void_p, C.c_uint32, c_dp, c_dp]),
+    "sbmbp_batch_get_field": (C.c_int, [C.c_void_p, C.c_uint32, c_dp]),
+    "sbmbp_batch_get_relaxation": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int), c_dp, c_dp]),
+    "sbmbp_batch_set_schedule": (C.c_int, [C.c_void_p, C.c_double, C.c_uint32]),
+    "sbmbp_batch_set_auto_relax": (C.c_int, [C.c_void_p, C.c_int]),
+    "sbmbp_batch_set_nonedge_mode": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "sbmbp_batch_sweep": (C.c_int, [C.c_void_p, C.c_double, C.c_uint32, c_dp]),
+    "sbmbp_batch_converge": (C.c_int, [C.c_void_p, C.c_double, C.c_uint32, C.c_double, C.POINTER(C.c_int), c_dp]),
+    "sbmbp_batch_free_energy": (C.c_int, [C.c_void_p, c_dp, c_dp]),
+    "sbmbp_batch_entropy": (C.c_int, [C.c_void_p, c_dp, c_dp]),
+    "sbmbp_batch_overlap": (C.c_int, [C.c_void_p, c_dp]),
+    "sbmbp_batch_em_expectations": (C.c_int, [C.c_void_p, C.c_uint32, c_dp, c_dp, c_dp]),
+    "sbmbp_batch_inference": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_float, C.POINTER(InferResult), c_u32p]),
+    "sbmbp_batch_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     # shard steps (sbm-bp_amd/distributed.py); desc/state structs are declared there
     "sbmbp_shard_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(ShardDesc), C.c_uint32, C.c_uint32, C.c_int]),
     "sbmbp_shard_begin": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),

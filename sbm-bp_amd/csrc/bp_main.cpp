@@ -4,7 +4,8 @@
 // Host code is C++14. Flags the reference parses but never reads (main.cpp:126-135)
 // are accepted and ignored. Extensions (default off, stdout unchanged): --precision, --device,
 // --gather, --field_mix, --check_every, --metrics_json, --schedule jacobi|coloured with --step_fraction (the sweep order of
-// sbmbp_set_sweep_order; single GPU), and --gpus N: the graph is sharded by vertex range over N GPUs of
+// sbmbp_set_sweep_order; single GPU), --restarts R (-m infer: R runs from seeds d .. d + R - 1 as one replica batch, sbmbp_batch_*;
+// the line printed is the run of lowest free energy), and --gpus N: the graph is sharded by vertex range over N GPUs of
 // this node, one host thread per GPU driving the C++ multi-GPU driver (sbmbp_dist_*, RCCL over xGMI); with fewer devices
 // than ranks the ranks share devices over the in-process transport (a rehearsal, not a speed-up).
 #include <chrono>
@@ -39,7 +40,7 @@ const opt_spec OPTS[] = {
     {"pa", 0, 2}, {"cab", 0, 2}, {"if_output_marginals", 0, 0}, {"mode", 'm', 1}, {"seed", 'd', 1}, {"help", 'h', 0},
     // extensions
     {"precision", 0, 1}, {"device", 0, 1}, {"gather", 0, 1}, {"field_mix", 0, 1}, {"check_every", 0, 1}, {"metrics_json", 0, 1},
-    {"gpus", 0, 1}, {"transport", 0, 1}, {"schedule", 0, 1}, {"step_fraction", 0, 1},
+    {"gpus", 0, 1}, {"transport", 0, 1}, {"schedule", 0, 1}, {"step_fraction", 0, 1}, {"restarts", 0, 1},
 };
 
 const opt_spec *find_long(const std::string &name) {
@@ -159,7 +160,9 @@ void usage(const char *argv0) {
                  "  --transport rccl|local  (default rccl; local = ranks may share devices, rehearsal)\n"
                  "  --schedule jacobi|coloured (=jacobi)  sweep order: synchronous, or coloured Gauss-Seidel with the field refreshed\n"
                  "                        inside a sweep (single GPU, up to 16 blocks)\n"
-                 "  --step_fraction arg (=0.125)  coloured order: rows updated between two field refreshes, as a fraction of N\n";
+                 "  --step_fraction arg (=0.125)  coloured order: rows updated between two field refreshes, as a fraction of N\n"
+                 "  --restarts arg (=1)   -m infer: this many runs from seeds d, d+1, ... advanced together as one replica batch; the\n"
+                 "                        output is that of the run with the lowest free energy (single GPU, jacobi, up to 16 blocks)\n";
 }
 
 bool read_column(const std::string &path, std::vector<long long> &out) {  // load_beliefs/load_confs (graph_utilities.cpp:8-40)
@@ -336,6 +339,83 @@ int main(int argc, char const *argv[]) {
     if (schedule == "coloured" && n_gpus > 1) {
         std::clog << "bp: --schedule coloured runs on one GPU only (the multi-GPU driver sweeps synchronously); drop --gpus or use --schedule jacobi\n";
         return 1;
+    }
+    const bool have_restarts = var_map.count("restarts") > 0;
+    const long long restarts = have_restarts ? (long long)num("restarts", 1) : 1;
+    if (have_restarts) {  // a replica batch (sbmbp_batch_*): what it cannot be combined with is said here, not by a later layer
+        const char *conflict = nullptr;
+        if (restarts < 1) conflict = "--restarts needs a value of at least 1";
+        else if (mode == "learn") conflict = "--restarts cannot be combined with -m learn (restarts are runs of -m infer)";
+        else if (n_gpus > 1) conflict = "--restarts cannot be combined with --gpus above 1 (a replica batch runs on one GPU)";
+        else if (schedule == "coloured") conflict = "--restarts cannot be combined with --schedule coloured (a replica batch sweeps synchronously)";
+        else if (Q > 16) conflict = "--restarts cannot be combined with more than 16 blocks (Q > 16)";
+        if (conflict) { std::clog << "bp: " << conflict << "\n"; return 1; }
+    }
+    if (restarts > 1) {
+        // ---- replica batch: R runs of -m infer over the one graph, seeds d .. d + R - 1 (include/sbmbp.h, "Replica batches") ----
+        const uint32_t R = uint32_t(restarts);
+        sbmbp_batch_t *bat = nullptr;
+        if ((rc = sbmbp_batch_create(&bat, graph, Q, deg_corr_flag, R, int(num("device", 0)))) != SBMBP_OK) return fail(rc);
+        stage("create batch (device)");
+        std::vector<uint32_t> seeds(R);
+        for (uint32_t r = 0; r < R; ++r) seeds[r] = seed + r;
+        if ((rc = sbmbp_batch_init_messages(bat, bp_messages_init_flag, beliefs.size() == N ? beliefs.data() : nullptr, true_conf.data(), seeds.data(), 1)) != SBMBP_OK)
+            return fail(rc);
+        stage("initial states + upload");
+        if ((rc = sbmbp_batch_set_params(bat, -1, cab_full.data(), na.data(), beta)) != SBMBP_OK) return fail(rc);
+        if ((rc = sbmbp_batch_set_schedule(bat, num("field_mix", 1.0), unsigned(num("check_every", 8)))) != SBMBP_OK) return fail(rc);
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<sbmbp_infer_result> res(R);
+        uint32_t best = 0;
+        if ((rc = sbmbp_batch_inference(bat, bp_conv_crit, time_conv, dumping_rate, res.data(), &best)) != SBMBP_OK) return fail(rc);
+        std::cout << signed_nan_like_reference(res[best].entropy) << " " << signed_nan_like_reference(res[best].free_energy) << " " << res[best].overlap
+                  << " " << res[best].niter << " \n";
+        if (if_output_marginals) {
+            std::vector<double> psi(size_t(N) * Q);
+            if ((rc = sbmbp_batch_get_state(bat, best, psi.data(), nullptr)) != SBMBP_OK) return fail(rc);
+            for (unsigned v = 0; v < N; ++v) {
+                for (unsigned q = 0; q < Q; ++q) std::cout << psi[size_t(v) * Q + q] << " ";
+                std::cout << "\n";
+            }
+            for (unsigned v = 0; v < N; ++v) {
+                double h = 0.0;
+                for (unsigned q = 0; q < Q; ++q) { const double p = psi[size_t(v) * Q + q]; if (p > 0) h -= p * std::log(p); }
+                std::clog << "Node-" << v << "; margEntropy H(v) is " << h << "\n";
+            }
+        }
+        stage("inference (all replicas)");
+        if (var_map.count("metrics_json")) {
+            const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            sbmbp_stats st;
+            sbmbp_batch_get_stats(bat, &st);
+            std::ofstream mj(var_map.get("metrics_json")[0].c_str());
+            auto jnum = [](double x) { std::ostringstream o; if (std::isfinite(x)) o << std::setprecision(17) << x; else o << "null"; return o.str(); };
+            mj << std::setprecision(12) << "{\"sweeps\":" << st.sweeps << ",\"edge_msg_updates\":" << st.edge_msg_updates
+               << ",\"marginal_gather_sweeps\":" << st.psi_form_sweeps << ",\"run_seconds\":" << secs
+               << ",\"bytes_per_sweep\":" << st.bytes_per_sweep << ",\"device_bytes\":" << st.device_bytes
+               << ",\"schedule\":\"jacobi\",\"restarts\":" << R << ",\"best\":" << best;
+            auto arr = [&](const char *name, const std::vector<std::string> &vals) {
+                mj << ",\"" << name << "\":[";
+                for (size_t k = 0; k < vals.size(); ++k) mj << (k ? "," : "") << vals[k];
+                mj << "]";
+            };
+            std::vector<std::string> a_seed, a_niter, a_f, a_ov, a_fl, a_gl;
+            for (uint32_t r = 0; r < R; ++r) {
+                int fl = 0, gl = -1;
+                (void)sbmbp_batch_get_relaxation(bat, r, &fl, &gl, nullptr, nullptr);
+                a_seed.push_back(std::to_string(seeds[r]));
+                a_niter.push_back(std::to_string(res[r].niter));
+                a_f.push_back(jnum(res[r].free_energy));
+                a_ov.push_back(jnum(res[r].overlap));
+                a_fl.push_back(std::to_string(fl));
+                a_gl.push_back(std::to_string(gl));
+            }
+            arr("seed", a_seed); arr("niter", a_niter); arr("free_energy", a_f); arr("overlap", a_ov); arr("field_level", a_fl); arr("generic_level", a_gl);
+            mj << "}\n";
+        }
+        sbmbp_batch_destroy(bat);
+        sbmbp_graph_destroy(graph);
+        return 0;
     }
     if (n_gpus > 1) {
         // ---- multi-GPU: one host thread per rank, all ranks make the same calls (include/sbmbp.h, "Multi-GPU") ----------

@@ -18,6 +18,7 @@
 #include "host_graph.h"
 #include "kernels.h"
 #include "kernels_wide.h"
+#include "kernels_batch.h"
 
 using namespace sbmbp;
 
@@ -1836,12 +1837,18 @@ int sbmbp_overlap(sbmbp_engine_t *e, double *ov) {
     return overlap_impl(e, ov, nullptr);
 }
 
+static int inference_reductions(sbmbp_engine *e, sbmbp_infer_result *out);
 int sbmbp_inference(sbmbp_engine_t *e, float conv_crit, uint32_t time_conv, float dumping_rate, sbmbp_infer_result *out) {
     device_scope dev_(e);
     if (!e || !out) return arg_error(__func__, __LINE__);
     NOT_SHARD(e);
     // belief_propagation::inference (bp.cpp:77-99); crit and damping arrive as float, compared as double (:406)
     CHK(run_sweeps(e, double(conv_crit), time_conv, double(dumping_rate), &out->niter, &out->last_maxdiff));
+    return inference_reductions(e, out);
+}
+
+// free energy, entropy and overlap of the state a converge call left (the second half of inference, bp.cpp:77-99)
+static int inference_reductions(sbmbp_engine *e, sbmbp_infer_result *out) {
     if (e->dc != 0) {  // entropy is NaN in the reference for deg_corr_flag != 0: only the free-energy pass runs
         CHK(free_energy_impl(e, &out->free_energy, nullptr));
         CHK(entropy_impl(e, &out->entropy, nullptr));
@@ -2658,6 +2665,446 @@ int sbmbp_shard_em_finish(sbmbp_engine_t *e, double *na_e, double *nna_e, double
     if (na_e) std::copy(na, na + Q, na_e);
     if (nna_e) std::copy(nna, nna + Q, nna_e);
     if (cab_e) std::copy(ce.begin(), ce.end(), cab_e);
+    return SBMBP_OK;
+}
+
+}  // extern "C"
+
+// =========================================== replica batches ===========================================
+// R independent BP states over one graph (sbmbp.h: sbmbp_batch_*; kernels_batch.h). The batch owns ONE engine: the graph
+// tables, the label vectors, the scratch of the reductions and the stream are that engine's. The engine's own message /
+// marginal / parameter buffers are replaced by the replica-major batch buffers, and for everything that is not the sweep
+// (initial state, state access, field, free energy, entropy, overlap, EM expectations) the engine is bound to replica r:
+// its state pointers then point into the batch buffers and its host mirrors hold replica r's parameters, so the existing
+// host code and reduction kernels run on replica r as they are.
+struct batch_replica {
+    std::vector<double> cab, eta;
+    std::vector<uint32_t> na;
+    double beta = 1.0;
+    bool have_params = false, have_state = false, field_fresh = false, w_positive = false;
+    int par = 0;                // which of the two buffers holds the current state
+    int ar_fl = 0, ar_gl = -1;  // levels the last converge call ended on
+};
+struct sbmbp_batch {
+    sbmbp_engine *e = nullptr;
+    uint32_t R = 0;
+    double *d_M = nullptr, *d_psi = nullptr, *d_rec = nullptr;
+    dev_params *d_P = nullptr;
+    int *d_par = nullptr;
+    uint32_t *d_cs = nullptr;  // [R] convergence states, gathered (k_batch_conv_states)
+    size_t msg_stride = 0, psi_stride = 0, rec_stride = 0;  // doubles per replica
+    std::vector<batch_replica> rep;
+    std::vector<int> call_par;  // parities at the start of the running call
+    void *h_cs = nullptr;       // page-locked: two slots of R convergence states
+    hipEvent_t ev_cs[2] = {nullptr, nullptr};
+    uint64_t sweeps = 0;
+};
+
+namespace {
+
+// binds the batch's engine to replica r for the lifetime of the object
+struct bound_replica {
+    sbmbp_batch *b;
+    uint32_t r;
+    bound_replica(sbmbp_batch *b_, uint32_t r_) : b(b_), r(r_) {
+        sbmbp_engine *e = b->e;
+        batch_replica &p = b->rep[r];
+        for (int k = 0; k < 2; ++k) {
+            e->d_M[k] = b->d_M + (size_t(k) * b->R + r) * b->msg_stride;
+            e->d_psi[k] = b->d_psi + (size_t(k) * b->R + r) * b->psi_stride;
+        }
+        e->d_P = b->d_P + r;
+        e->cur = e->pcur = p.par;
+        e->cab = p.cab; e->eta = p.eta; e->na = p.na; e->beta = p.beta;
+        e->have_params = p.have_params; e->have_state = p.have_state; e->field_fresh = p.field_fresh; e->w_positive = p.w_positive;
+        e->ar_fl = p.ar_fl; e->ar_gl = p.ar_gl;
+        e->psi_consistent = false; e->init_from_psi = false; e->fz.valid = false;  // message-gather form only
+    }
+    ~bound_replica() {
+        sbmbp_engine *e = b->e;
+        batch_replica &p = b->rep[r];
+        p.cab = e->cab; p.eta = e->eta; p.na = e->na; p.beta = e->beta;
+        p.have_params = e->have_params; p.have_state = e->have_state; p.field_fresh = e->field_fresh; p.w_positive = e->w_positive;
+        p.par = e->cur;
+        e->d_M[0] = e->d_M[1] = e->d_psi[0] = e->d_psi[1] = nullptr;
+        e->d_P = nullptr;
+        e->have_state = e->have_params = false;
+    }
+};
+
+batch_view view_of(const sbmbp_batch *b) {
+    return batch_view{b->d_M, b->d_psi, b->d_P, b->d_rec, b->d_par, b->msg_stride, b->psi_stride, b->rec_stride, b->R};
+}
+
+int batch_replica_arg(const sbmbp_batch *b, int64_t replica) {
+    if (replica < 0 || replica >= int64_t(b->R)) {
+        set_error("replica index " + std::to_string(replica) + " outside the batch of " + std::to_string(b->R));
+        return SBMBP_ERR_ARG;
+    }
+    return SBMBP_OK;
+}
+
+// sweep j of the running call for all replicas: hub rows per replica (the single engine's fragment pair on offset
+// pointers), ONE frame launch, ONE fold + update launch
+int batch_launch_sweep(sbmbp_batch *b, const batch_view &bv, uint32_t j, double damp) {
+    sbmbp_engine *e = b->e;
+    const int32_t *clamp = e->has_clamp ? e->d_clamp : nullptr;
+    if (e->n_hub) {
+        double *keep = e->d_partials;
+        int r_ = SBMBP_OK;
+        for (uint32_t r = 0; r < b->R && r_ == SBMBP_OK; ++r) {
+            const int mc = (b->call_par[r] + int(j)) & 1;
+            e->d_P = b->d_P + r;
+            e->d_partials = b->d_rec + size_t(r) * b->rec_stride;
+            r_ = launch_hub_msg(e, e->stream, b->d_M + (size_t(mc) * b->R + r) * b->msg_stride, b->d_M + (size_t(mc ^ 1) * b->R + r) * b->msg_stride,
+                                b->d_psi + (size_t(mc) * b->R + r) * b->psi_stride, b->d_psi + (size_t(mc ^ 1) * b->R + r) * b->psi_stride, clamp, damp);
+        }
+        e->d_P = nullptr;
+        e->d_partials = keep;
+        CHK(r_);
+    }
+    const dim3 grid(e->n_blk, b->R);
+    if (e->dc == 2) {
+        DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_batch<QQ, true>), grid, dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
+                                            e->d_deg, clamp, e->d_blk_row, e->d_blk_e0, bv.M, bv.psi, bv.P, bv.rec, bv.par, bv.msg_stride, bv.psi_stride,
+                                            bv.rec_stride, bv.R, j, 1, damp));
+    } else {
+        DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_batch<QQ, false>), grid, dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
+                                            e->d_deg, clamp, e->d_blk_row, e->d_blk_e0, bv.M, bv.psi, bv.P, bv.rec, bv.par, bv.msg_stride, bv.psi_stride,
+                                            bv.rec_stride, bv.R, j, int(e->dc), damp));
+    }
+    DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_finalize_batch<QQ>), dim3(b->R), dim3(BLOCK), 0, e->stream, bv.P, bv.rec, bv.rec_stride, e->n_blk));
+    HIPCHK(hipGetLastError());
+    return SBMBP_OK;
+}
+
+// run_sweeps for the batch: every replica starts from its current state, stops at its own sweep (device side, P[r].stop)
+// and keeps the state of that sweep; the call ends when all have stopped or after max_sweeps
+int batch_run(sbmbp_batch *b, double crit, uint32_t max_sweeps, double damping, int *niter, double *last) {
+    sbmbp_engine *e = b->e;
+    const uint32_t R = b->R;
+    for (uint32_t r = 0; r < R; ++r)
+        if (!b->rep[r].have_params || !b->rep[r].have_state) {
+            set_error("set_params and init_messages/set_state must precede converge (replica " + std::to_string(r) + ")");
+            return SBMBP_ERR_STATE;
+        }
+    CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (e->Q + 1)));
+    b->call_par.resize(R);
+    for (uint32_t r = 0; r < R; ++r) {  // parameter block and initial field of every replica (once per call: a loop)
+        bound_replica v(b, r);
+        CHK(upload_params(e, crit, false));
+        CHK(launch_field(e, 1));
+        b->call_par[r] = b->rep[r].par;
+    }
+    HIPCHK(hipMemcpyAsync(b->d_par, b->call_par.data(), size_t(R) * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const batch_view bv = view_of(b);
+    conv_state *slots = static_cast<conv_state *>(b->h_cs);
+    std::vector<conv_state> cs(R, conv_state{0.0, -1, 0, 0, 0, 0, 0, 1, 0, 0, -1});
+    uint32_t done = 0;
+    const uint32_t batch_max = std::max<uint32_t>(1, e->check_every);
+    // batches are queued one ahead, as in run_sweeps: the GPU never idles while the host reads the states
+    auto queue_batch = [&](int slot) -> int {
+        const uint32_t n = std::min(batch_max, max_sweeps - done);
+        for (uint32_t k = 0; k < n; ++k) CHK(batch_launch_sweep(b, bv, done + k, damping));
+        done += n;
+        constexpr uint32_t words = sizeof(conv_state) / 4;
+        hipLaunchKernelGGL(k_batch_conv_states, dim3(std::min<uint32_t>(64, (R * words + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, e->stream, b->d_P, R,
+                           uint32_t(offsetof(dev_params, maxdiff)), words, b->d_cs);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(slots + size_t(slot) * R, b->d_cs, size_t(R) * sizeof(conv_state), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipEventRecord(b->ev_cs[slot], e->stream));
+        return SBMBP_OK;
+    };
+    auto all_stopped = [&](const conv_state *s) {
+        for (uint32_t r = 0; r < R; ++r) if (!s[r].stop) return false;
+        return true;
+    };
+    if (max_sweeps > 0) {
+        CHK(queue_batch(0));
+        for (int k = 0;; ++k) {
+            const bool more = done < max_sweeps;
+            if (more) CHK(queue_batch((k + 1) & 1));
+            HIPCHK(hipEventSynchronize(b->ev_cs[k & 1]));
+            const conv_state *s = slots + size_t(k & 1) * R;
+            if (all_stopped(s) || !more) {
+                if (more) {  // drain the batch queued ahead (no-ops: every replica has stopped)
+                    HIPCHK(hipEventSynchronize(b->ev_cs[(k + 1) & 1]));
+                    s = slots + size_t((k + 1) & 1) * R;
+                }
+                std::copy(s, s + R, cs.begin());
+                break;
+            }
+        }
+    }
+    for (uint32_t r = 0; r < R; ++r) {
+        batch_replica &p = b->rep[r];
+        const uint32_t executed = uint32_t(cs[r].sweep_idx);
+        p.par = (p.par + int(executed)) & 1;
+        b->sweeps += executed;
+        const bool relaxed = cs[r].ar_fl > 0 || cs[r].ar_gl >= 0;
+        p.field_fresh = (e->field_mix >= 1.0) && !relaxed && executed > 0;
+        p.ar_fl = cs[r].ar_fl;
+        p.ar_gl = cs[r].ar_gl;
+        if (niter) niter[r] = cs[r].conv_iter;
+        if (last) last[r] = cs[r].maxdiff;  // message-gather sweeps report the 1-step difference
+    }
+    return SBMBP_OK;
+}
+
+void batch_free(sbmbp_batch *b) {
+    if (!b) return;
+    if (b->e) {
+        (void)hipSetDevice(b->e->device);
+        if (b->e->stream) (void)hipStreamSynchronize(b->e->stream);
+        b->e->d_M[0] = b->e->d_M[1] = b->e->d_psi[0] = b->e->d_psi[1] = nullptr;  // they pointed into the batch buffers
+        b->e->d_P = nullptr;
+    }
+    void *ptrs[] = {b->d_M, b->d_psi, b->d_rec, b->d_P, b->d_par, b->d_cs};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    if (b->h_cs) (void)hipHostFree(b->h_cs);
+    for (auto ev : b->ev_cs) if (ev) (void)hipEventDestroy(ev);
+    if (b->e) sbmbp_destroy(b->e);
+    delete b;
+}
+
+}  // namespace
+
+#define BATCH_ARGS(b) do { if (!(b)) return arg_error(__func__, __LINE__); } while (0)
+
+extern "C" {
+
+int sbmbp_batch_create(sbmbp_batch_t **out, const sbmbp_graph_t *g, uint32_t Q, uint32_t dc, uint32_t n_replicas, int device) {
+    if (!out || !g) return arg_error(__func__, __LINE__);
+    *out = nullptr;
+    if (n_replicas == 0) { set_error("a replica batch needs n_replicas >= 1"); return SBMBP_ERR_ARG; }
+    if (n_replicas > 65535) { set_error("n_replicas above 65535: the replica index is the second grid dimension of the sweep launch"); return SBMBP_ERR_ARG; }
+    if (Q < 2) { set_error("Q must be at least 2"); return SBMBP_ERR_ARG; }
+    if (dc > 2) { set_error("deg_corr_flag must be 0, 1 or 2"); return SBMBP_ERR_ARG; }
+    if (Q > 16) { set_error("replica batches are implemented up to Q = 16 (the lane-per-edge kernels); Q = " + std::to_string(Q)); return SBMBP_ERR_UNSUPPORTED; }
+    sbmbp_engine *e = nullptr;
+    CHK(sbmbp_create(&e, g, Q, dc, device));
+    device_scope dev_(e);
+    auto *b = new sbmbp_batch();
+    b->e = e;
+    b->R = n_replicas;
+    // the engine's own state buffers give way to the batch's
+    void *own[] = {e->d_M[0], e->d_M[1], e->d_psi[0], e->d_psi[1], e->d_P};
+    for (void *p : own) if (p) (void)hipFree(p);
+    e->device_bytes -= (2 * std::max<uint64_t>(e->E2, 1) * (Q - 1) + 2 * uint64_t(e->N) * Q) * 8 + sizeof(dev_params);
+    e->d_M[0] = e->d_M[1] = e->d_psi[0] = e->d_psi[1] = nullptr;
+    e->d_P = nullptr;
+    e->gather_mode = 1;  // message-gather form only: the reductions of a bound replica take the message-gather kernels too
+    b->msg_stride = size_t(std::max<uint64_t>(e->E2, 1)) * (Q - 1);  // >= one record: the sweep's loads are branch-free
+    b->psi_stride = size_t(e->N) * Q;
+    b->rec_stride = size_t(std::max<uint32_t>(e->n_blk, 1)) * (Q + 1);
+    const uint64_t R = n_replicas;
+    const uint64_t need = R * (2 * uint64_t(b->msg_stride) + 2 * uint64_t(b->psi_stride)) * 8;
+    size_t free_b = 0, total_b = 0;
+    int r = SBMBP_OK;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b) {
+        set_error("a batch of " + std::to_string(R) + " replicas needs " + std::to_string(need) + " B of HBM for its states, " + std::to_string(free_b) + " B are free");
+        r = SBMBP_ERR_NOMEM;
+    }
+    if (r == SBMBP_OK) r = dev_alloc(e, &b->d_M, 2 * R * b->msg_stride);
+    if (r == SBMBP_OK) r = dev_alloc(e, &b->d_psi, 2 * R * b->psi_stride);
+    if (r == SBMBP_OK) r = dev_alloc(e, &b->d_rec, R * b->rec_stride);
+    if (r == SBMBP_OK) r = dev_alloc(e, &b->d_P, R);
+    if (r == SBMBP_OK) r = dev_alloc(e, &b->d_par, R);
+    if (r == SBMBP_OK) r = dev_alloc(e, &b->d_cs, R * (sizeof(conv_state) / 4));
+    hipError_t h = hipSuccess;
+    if (r == SBMBP_OK) h = hipMemsetAsync(b->d_rec, 0, R * b->rec_stride * 8, e->stream);
+    if (r == SBMBP_OK && h == hipSuccess) h = hipMemsetAsync(b->d_P, 0, R * sizeof(dev_params), e->stream);
+    if (r == SBMBP_OK && h == hipSuccess) h = hipMemsetAsync(b->d_par, 0, R * sizeof(int), e->stream);
+    if (r == SBMBP_OK && h == hipSuccess) h = hipHostMalloc(&b->h_cs, 2 * R * sizeof(conv_state), hipHostMallocDefault);
+    for (auto &ev : b->ev_cs) if (r == SBMBP_OK && h == hipSuccess) h = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (r == SBMBP_OK && h == hipSuccess) h = hipStreamSynchronize(e->stream);
+    if (r == SBMBP_OK && h != hipSuccess) { set_error(std::string("sbmbp_batch_create: ") + hipGetErrorString(h)); r = SBMBP_ERR_HIP; }
+    if (r != SBMBP_OK) { batch_free(b); return r; }
+    b->rep.resize(n_replicas);
+    *out = b;
+    return SBMBP_OK;
+}
+
+void sbmbp_batch_destroy(sbmbp_batch_t *b) { batch_free(b); }
+
+uint32_t sbmbp_batch_num_replicas(const sbmbp_batch_t *b) { return b ? b->R : 0; }
+
+int sbmbp_batch_init_messages(sbmbp_batch_t *b, uint32_t flag, const int32_t *conf, const uint32_t *true_conf, const uint32_t *seeds,
+                              int conditional) {
+    if (!b || !seeds) return arg_error(__func__, __LINE__);
+    device_scope dev_(b->e);
+    for (uint32_t r = 0; r < b->R; ++r) {
+        bound_replica v(b, r);
+        CHK(sbmbp_init_messages(b->e, flag, conf, true_conf, seeds[r], conditional));
+    }
+    return SBMBP_OK;
+}
+int sbmbp_batch_init_messages_device(sbmbp_batch_t *b, const uint64_t *seeds, const uint32_t *true_conf) {
+    if (!b || !seeds) return arg_error(__func__, __LINE__);
+    device_scope dev_(b->e);
+    for (uint32_t r = 0; r < b->R; ++r) {
+        bound_replica v(b, r);
+        CHK(sbmbp_init_messages_device(b->e, seeds[r], true_conf));
+    }
+    return SBMBP_OK;
+}
+
+int sbmbp_batch_set_params(sbmbp_batch_t *b, int replica, const double *cab, const uint32_t *na, double beta) {
+    if (!b || !cab || !na) return arg_error(__func__, __LINE__);
+    if (replica != -1) CHK(batch_replica_arg(b, replica));
+    device_scope dev_(b->e);
+    for (uint32_t r = 0; r < b->R; ++r) {
+        if (replica != -1 && uint32_t(replica) != r) continue;
+        bound_replica v(b, r);
+        CHK(sbmbp_set_params(b->e, cab, na, beta));
+    }
+    return SBMBP_OK;
+}
+int sbmbp_batch_get_params(sbmbp_batch_t *b, uint32_t replica, double *cab, uint32_t *na, double *beta) {
+    BATCH_ARGS(b);
+    CHK(batch_replica_arg(b, replica));
+    const batch_replica &p = b->rep[replica];
+    if (!p.have_params) return SBMBP_ERR_STATE;
+    if (cab) std::copy(p.cab.begin(), p.cab.end(), cab);
+    if (na) std::copy(p.na.begin(), p.na.end(), na);
+    if (beta) *beta = p.beta;
+    return SBMBP_OK;
+}
+
+int sbmbp_batch_set_state(sbmbp_batch_t *b, uint32_t replica, const double *psi, const double *msg_out) {
+    BATCH_ARGS(b);
+    CHK(batch_replica_arg(b, replica));
+    device_scope dev_(b->e);
+    bound_replica v(b, replica);
+    return sbmbp_set_state(b->e, psi, msg_out);
+}
+int sbmbp_batch_get_state(sbmbp_batch_t *b, uint32_t replica, double *psi, double *msg_out) {
+    BATCH_ARGS(b);
+    CHK(batch_replica_arg(b, replica));
+    device_scope dev_(b->e);
+    bound_replica v(b, replica);
+    return sbmbp_get_state(b->e, psi, msg_out);
+}
+int sbmbp_batch_get_field(sbmbp_batch_t *b, uint32_t replica, double *h) {
+    if (!b || !h) return arg_error(__func__, __LINE__);
+    CHK(batch_replica_arg(b, replica));
+    device_scope dev_(b->e);
+    bound_replica v(b, replica);
+    return sbmbp_get_field(b->e, h);
+}
+int sbmbp_batch_get_relaxation(const sbmbp_batch_t *b, uint32_t replica, int *field_level, int *generic_level, double *field_mix,
+                               double *damping_factor) {
+    BATCH_ARGS(b);
+    CHK(batch_replica_arg(b, replica));
+    const batch_replica &p = b->rep[replica];
+    if (field_level) *field_level = p.ar_fl;
+    if (generic_level) *generic_level = p.ar_gl;
+    if (field_mix) *field_mix = std::min(std::min(b->e->field_mix, ar_field_cap(p.ar_fl)), ar_gen_mix(p.ar_gl));
+    if (damping_factor) *damping_factor = ar_gen_damp(p.ar_gl);
+    return SBMBP_OK;
+}
+
+int sbmbp_batch_set_schedule(sbmbp_batch_t *b, double field_mix, uint32_t check_every) {
+    BATCH_ARGS(b);
+    return sbmbp_set_schedule(b->e, field_mix, check_every);
+}
+int sbmbp_batch_set_auto_relax(sbmbp_batch_t *b, int on) {
+    BATCH_ARGS(b);
+    return sbmbp_set_auto_relax(b->e, on);
+}
+int sbmbp_batch_set_nonedge_mode(sbmbp_batch_t *b, int nonedge_mode, int series_order) {
+    BATCH_ARGS(b);
+    return sbmbp_set_nonedge_mode(b->e, nonedge_mode, series_order);
+}
+
+int sbmbp_batch_sweep(sbmbp_batch_t *b, double damping, uint32_t n_sweeps, double *last) {
+    BATCH_ARGS(b);
+    device_scope dev_(b->e);
+    const uint32_t keep = b->e->check_every;
+    b->e->check_every = std::max<uint32_t>(keep, 64);  // no convergence test: sync rarely
+    const int r = batch_run(b, -1.0, n_sweeps, damping, nullptr, last);
+    b->e->check_every = keep;
+    return r;
+}
+int sbmbp_batch_converge(sbmbp_batch_t *b, double crit, uint32_t max_sweeps, double damping, int *niter, double *last) {
+    BATCH_ARGS(b);
+    device_scope dev_(b->e);
+    return batch_run(b, crit, max_sweeps, damping, niter, last);
+}
+
+int sbmbp_batch_free_energy(sbmbp_batch_t *b, double *f, double *parts) {
+    BATCH_ARGS(b);
+    device_scope dev_(b->e);
+    for (uint32_t r = 0; r < b->R; ++r) {
+        bound_replica v(b, r);
+        CHK(free_energy_impl(b->e, f ? f + r : nullptr, parts ? parts + 3 * size_t(r) : nullptr));
+    }
+    return SBMBP_OK;
+}
+int sbmbp_batch_entropy(sbmbp_batch_t *b, double *ent, double *parts) {
+    BATCH_ARGS(b);
+    device_scope dev_(b->e);
+    for (uint32_t r = 0; r < b->R; ++r) {
+        bound_replica v(b, r);
+        CHK(entropy_impl(b->e, ent ? ent + r : nullptr, parts ? parts + 3 * size_t(r) : nullptr));
+    }
+    return SBMBP_OK;
+}
+int sbmbp_batch_overlap(sbmbp_batch_t *b, double *ov) {
+    if (!b || !ov) return arg_error(__func__, __LINE__);
+    device_scope dev_(b->e);
+    for (uint32_t r = 0; r < b->R; ++r) {
+        bound_replica v(b, r);
+        CHK(overlap_impl(b->e, ov + r, nullptr));
+    }
+    return SBMBP_OK;
+}
+int sbmbp_batch_em_expectations(sbmbp_batch_t *b, uint32_t replica, double *na_e, double *nna_e, double *cab_e) {
+    BATCH_ARGS(b);
+    CHK(batch_replica_arg(b, replica));
+    device_scope dev_(b->e);
+    bound_replica v(b, replica);
+    return em_expect(b->e, na_e, nna_e, cab_e);
+}
+
+int sbmbp_batch_inference(sbmbp_batch_t *b, float conv_crit, uint32_t time_conv, float dumping_rate, sbmbp_infer_result *out, uint32_t *best) {
+    if (!b || !out) return arg_error(__func__, __LINE__);
+    device_scope dev_(b->e);
+    std::vector<int> niter(b->R);
+    std::vector<double> last(b->R);
+    CHK(batch_run(b, double(conv_crit), time_conv, double(dumping_rate), niter.data(), last.data()));
+    for (uint32_t r = 0; r < b->R; ++r) {
+        bound_replica v(b, r);
+        out[r].niter = niter[r];
+        out[r].last_maxdiff = last[r];
+        CHK(inference_reductions(b->e, &out[r]));
+    }
+    if (best) {  // lowest free energy among the converged replicas (among all when none converged); NaN never; ties: lowest index
+        int pick = -1;
+        for (int pass = 0; pass < 2 && pick < 0; ++pass)
+            for (uint32_t r = 0; r < b->R; ++r) {
+                if (pass == 0 && out[r].niter < 0) continue;
+                if (std::isnan(out[r].free_energy)) continue;
+                if (pick < 0 || out[r].free_energy < out[pick].free_energy) pick = int(r);
+            }
+        *best = pick < 0 ? 0u : uint32_t(pick);
+    }
+    return SBMBP_OK;
+}
+
+int sbmbp_batch_get_stats(sbmbp_batch_t *b, sbmbp_stats *out) {
+    if (!b || !out) return arg_error(__func__, __LINE__);
+    const sbmbp_engine *e = b->e;
+    std::memset(out, 0, sizeof *out);
+    out->sweeps = b->sweeps;  // replica-sweeps actually executed
+    out->edge_msg_updates = b->sweeps * e->E2;
+    out->bytes_per_sweep = double(e->E2) * (24.0 * e->Q + 4.0 + (e->dc == 2 ? 4.0 : 0.0)) + double(e->N) * (8.0 * e->Q + 8.0);  // of ONE replica
+    out->device_bytes = e->device_bytes;
+    out->n_blocks = e->n_blk;
+    out->n_hub_rows = e->n_hub;
+    out->hub_edges = e->hub_edges;
+    out->psi_form_sweeps = 0;
     return SBMBP_OK;
 }
 
