@@ -216,6 +216,17 @@ int sbmbp_learning(sbmbp_engine_t *e, float learning_conv_crit, uint32_t learnin
  * plain Jacobi). snap: the integer truncation of the group sizes (belief_propagation.cpp:58-63) treats a value within
  * min(snap * N * learning_conv_crit, 0.01) BELOW an integer as that integer (default snap = 1; 0 = truncate exactly). */
 int sbmbp_set_learning_schedule(sbmbp_engine_t *e, double field_mix, double snap);
+/* host only, no device: one learning_step (belief_propagation.cpp:53-75 with the snap rule above); na / cab in and out.
+ * Group i < Q - 1 becomes unsigned(int(learning_rate * na_expect[i] + (1 - learning_rate) * na[i] + s)) with
+ * s = min(snap * n_vertices * crit, 0.01) (:58-63), the last group takes the rest (:64), and cab is mixed entry by entry
+ * (:66-72). sbmbp_learning and sbmbp_batch_learning run exactly this function. */
+int sbmbp_learning_step_host(uint32_t Q, uint32_t n_vertices, double learning_rate, double snap, double crit,
+                             const double *na_expect, const double *cab_expect, uint32_t *na, double *cab);
+/* host only, no device: which of n runs over one graph is best. Passes k = 0 .. n_ranks - 1 look at the runs with
+ * rank[r] == k (a negative rank is never looked at) and the first pass with a candidate ends the search: its lowest free
+ * energy wins, a NaN free energy is never best, ties go to the lowest index. No candidate at all: *best = 0.
+ * sbmbp_batch_inference ranks converged runs 0 and the others 1; sbmbp_batch_learning ranks status 1 as 0, status 0 as 1. */
+int sbmbp_best_replica(uint32_t n, const double *free_energy, const int *rank, int n_ranks, uint32_t *best);
 
 /* counters for the metric "BP edge-message updates per second" */
 typedef struct sbmbp_stats {
@@ -290,6 +301,23 @@ int sbmbp_batch_inference(sbmbp_batch_t *b, float conv_crit, uint32_t time_conv,
 /* sweeps = sum over replicas of the sweeps actually executed, edge_msg_updates = sweeps * E2, psi_form_sweeps = 0;
  * bytes_per_sweep is one replica's; the kernel-time fields are 0 */
 int sbmbp_batch_get_stats(sbmbp_batch_t *b, sbmbp_stats *out);
+
+/* Multi-start EM: belief_propagation::learning (belief_propagation.cpp:14-75) for every replica in lock-step rounds.
+ * Round t: every replica still learning applies `if (fdiff < crit) crit *= 0.1` (:29-31) to its OWN criterion; ONE batched
+ * BP run advances them all (per-replica criterion; replicas that have stopped learning are frozen: state, parity and
+ * parameter block untouched); ONE launch sequence yields the reductions of all of them (kernels_batch.h) and one copy
+ * brings them to the host, where each replica runs the stop tests (:38-45) or sbmbp_learning_step_host (:53-75).
+ * Replica r goes through the states, parameters, em_steps, status and total_sweeps of a single engine in message-gather
+ * form (sbmbp_set_gather_mode(e, 1)) with the same schedule started from its state and parameters, up to the summation
+ * order of the reductions. SBMBP_ERR_STATE: a replica has no parameters or no state. */
+int sbmbp_batch_set_learning_schedule(sbmbp_batch_t *b, double field_mix, double snap);   /* common to all replicas */
+/* the reductions of one EM step for every replica from one launch sequence: na_expect / nna_expect R*Q, cab_expect R*Q*Q,
+ * f R, parts 3R; any pointer may be NULL */
+int sbmbp_batch_em_step(sbmbp_batch_t *b, double *na_expect, double *nna_expect, double *cab_expect, double *f, double *parts);
+/* out[R]; eta R*Q and cab R*Q*Q as the reference prints them (:48-49); *best: lowest free energy among status 1, else
+ * among status 0, a NaN free energy never, ties to the lowest index */
+int sbmbp_batch_learning(sbmbp_batch_t *b, float learning_conv_crit, uint32_t learning_max_time, float learning_rate,
+                         float dumping_rate, sbmbp_learn_result *out, double *eta, double *cab, uint32_t *best);
 
 /* ---------------------------------------------------------------------------------------------
  * Vertex-range sharding: the per-shard STEPS (one engine per GPU). No reference counterpart: the

@@ -524,6 +524,28 @@ class ReplicaBatch:
         check(self._lib.sbmbp_batch_em_expectations(self._h, self._replica(replica), _dp(na), _dp(nna), _dp(cabe) if cab else None))
         return na, nna, cabe
 
+    def set_learning_schedule(self, field_mix=0.3, snap=1.0):
+        """the two schedule rules of the EM loop (BeliefPropagation.set_learning_schedule), common to all replicas"""
+        check(self._lib.sbmbp_batch_set_learning_schedule(self._h, field_mix, snap))
+
+    def em_step(self):
+        """the reductions of one EM step for every replica from one launch sequence:
+        (na_expect [R, Q], nna_expect [R, Q], cab_expect [R, Q, Q], free energy [R], its parts [R, 3])"""
+        na, nna = np.zeros((self.R, self.Q)), np.zeros((self.R, self.Q))
+        cabe, f, parts = np.zeros((self.R, self.Q, self.Q)), np.zeros(self.R), np.zeros((self.R, 3))
+        check(self._lib.sbmbp_batch_em_step(self._h, _dp(na), _dp(nna), _dp(cabe), _dp(f), _dp(parts)))
+        return na, nna, cabe, f, parts
+
+    def learning(self, learning_conv_crit, learning_max_time, learning_rate, dumping_rate):
+        """multi-start EM: every replica learns from its own state and parameters, in lock-step rounds.
+        Returns (list of R LearnResult, eta [R, Q], cab [R, Q, Q], index of the best replica)."""
+        res = (LearnResult * self.R)()
+        eta, cab = np.zeros((self.R, self.Q)), np.zeros((self.R, self.Q, self.Q))
+        best = C.c_uint32(0)
+        check(self._lib.sbmbp_batch_learning(self._h, learning_conv_crit, learning_max_time, learning_rate, dumping_rate, res, _dp(eta), _dp(cab),
+                                             C.byref(best)))
+        return list(res), eta, cab, best.value
+
     def inference(self, conv_crit, time_conv, dumping_rate):
         """inference of every replica: (list of R result structs, index of the replica of lowest free energy)"""
         res = (InferResult * self.R)()

@@ -5,7 +5,8 @@
 // are accepted and ignored. Extensions (default off, stdout unchanged): --precision, --device,
 // --gather, --field_mix, --check_every, --metrics_json, --schedule jacobi|coloured with --step_fraction (the sweep order of
 // sbmbp_set_sweep_order; single GPU), --restarts R (-m infer: R runs from seeds d .. d + R - 1 as one replica batch, sbmbp_batch_*;
-// the line printed is the run of lowest free energy), and --gpus N: the graph is sharded by vertex range over N GPUs of
+// the line printed is the run of lowest free energy), --learn_restarts R (-m learn: R EM runs from seeds d .. d + R - 1 as one
+// replica batch, sbmbp_batch_learning; the two lines printed are those of the best run), and --gpus N: the graph is sharded by vertex range over N GPUs of
 // this node, one host thread per GPU driving the C++ multi-GPU driver (sbmbp_dist_*, RCCL over xGMI); with fewer devices
 // than ranks the ranks share devices over the in-process transport (a rehearsal, not a speed-up).
 #include <chrono>
@@ -41,6 +42,7 @@ const opt_spec OPTS[] = {
     // extensions
     {"precision", 0, 1}, {"device", 0, 1}, {"gather", 0, 1}, {"field_mix", 0, 1}, {"check_every", 0, 1}, {"metrics_json", 0, 1},
     {"gpus", 0, 1}, {"transport", 0, 1}, {"schedule", 0, 1}, {"step_fraction", 0, 1}, {"restarts", 0, 1},
+    {"learn_restarts", 0, 1},
 };
 
 const opt_spec *find_long(const std::string &name) {
@@ -162,7 +164,10 @@ void usage(const char *argv0) {
                  "                        inside a sweep (single GPU, up to 16 blocks)\n"
                  "  --step_fraction arg (=0.125)  coloured order: rows updated between two field refreshes, as a fraction of N\n"
                  "  --restarts arg (=1)   -m infer: this many runs from seeds d, d+1, ... advanced together as one replica batch; the\n"
-                 "                        output is that of the run with the lowest free energy (single GPU, jacobi, up to 16 blocks)\n";
+                 "                        output is that of the run with the lowest free energy (single GPU, jacobi, up to 16 blocks)\n"
+                 "  --learn_restarts arg (=1)  -m learn: this many EM runs from seeds d, d+1, ... with the command line's initial parameters,\n"
+                 "                        advanced together as one replica batch; the output is that of the best run: lowest free energy\n"
+                 "                        among the runs that stopped on fdiff < learning_conv_crit (single GPU, jacobi, up to 16 blocks)\n";
 }
 
 bool read_column(const std::string &path, std::vector<long long> &out) {  // load_beliefs/load_confs (graph_utilities.cpp:8-40)
@@ -351,6 +356,17 @@ int main(int argc, char const *argv[]) {
         else if (Q > 16) conflict = "--restarts cannot be combined with more than 16 blocks (Q > 16)";
         if (conflict) { std::clog << "bp: " << conflict << "\n"; return 1; }
     }
+    const bool have_lrestarts = var_map.count("learn_restarts") > 0;
+    const long long lrestarts = have_lrestarts ? (long long)num("learn_restarts", 1) : 1;
+    if (have_lrestarts) {  // a replica batch that learns (sbmbp_batch_learning)
+        const char *conflict = nullptr;
+        if (lrestarts < 1) conflict = "--learn_restarts needs a value of at least 1";
+        else if (mode == "infer") conflict = "--learn_restarts cannot be combined with -m infer (they are runs of -m learn; -m infer has --restarts)";
+        else if (n_gpus > 1) conflict = "--learn_restarts cannot be combined with --gpus above 1 (a replica batch runs on one GPU)";
+        else if (schedule == "coloured") conflict = "--learn_restarts cannot be combined with --schedule coloured (a replica batch sweeps synchronously)";
+        else if (Q > 16) conflict = "--learn_restarts cannot be combined with more than 16 blocks (Q > 16)";
+        if (conflict) { std::clog << "bp: " << conflict << "\n"; return 1; }
+    }
     if (restarts > 1) {
         // ---- replica batch: R runs of -m infer over the one graph, seeds d .. d + R - 1 (include/sbmbp.h, "Replica batches") ----
         const uint32_t R = uint32_t(restarts);
@@ -411,6 +427,68 @@ int main(int argc, char const *argv[]) {
                 a_gl.push_back(std::to_string(gl));
             }
             arr("seed", a_seed); arr("niter", a_niter); arr("free_energy", a_f); arr("overlap", a_ov); arr("field_level", a_fl); arr("generic_level", a_gl);
+            mj << "}\n";
+        }
+        sbmbp_batch_destroy(bat);
+        sbmbp_graph_destroy(graph);
+        return 0;
+    }
+    if (lrestarts > 1) {
+        // ---- replica batch: R runs of -m learn over the one graph, seeds d .. d + R - 1, the command line's initial parameters ----
+        const uint32_t R = uint32_t(lrestarts);
+        sbmbp_batch_t *bat = nullptr;
+        if ((rc = sbmbp_batch_create(&bat, graph, Q, deg_corr_flag, R, int(num("device", 0)))) != SBMBP_OK) return fail(rc);
+        stage("create batch (device)");
+        std::vector<uint32_t> seeds(R);
+        for (uint32_t r = 0; r < R; ++r) seeds[r] = seed + r;
+        if ((rc = sbmbp_batch_init_messages(bat, bp_messages_init_flag, beliefs.size() == N ? beliefs.data() : nullptr, true_conf.data(), seeds.data(), 0)) != SBMBP_OK)
+            return fail(rc);
+        stage("initial states + upload");
+        if ((rc = sbmbp_batch_set_params(bat, -1, cab_full.data(), na.data(), beta)) != SBMBP_OK) return fail(rc);
+        if ((rc = sbmbp_batch_set_schedule(bat, num("field_mix", 1.0), unsigned(num("check_every", 8)))) != SBMBP_OK) return fail(rc);
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<sbmbp_learn_result> res(R);
+        std::vector<double> eta_out(size_t(R) * Q), cab_out(size_t(R) * Q * Q);
+        uint32_t best = 0;
+        if ((rc = sbmbp_batch_learning(bat, learning_conv_crit, time_conv, learning_rate, dumping_rate, res.data(), eta_out.data(), cab_out.data(), &best)) != SBMBP_OK)
+            return fail(rc);
+        if (res[best].status == 2) std::clog << "Bethe energy is calculated as nan.\n";
+        if (res[best].status == 1) std::clog << "Algorithm stop because of fdiff < learning_conv_crit. [which is good]\n";
+        for (uint32_t r = 0; r < R; ++r)
+            std::clog << "restart " << r << ": seed " << seeds[r] << " em_steps " << res[r].em_steps << " status " << res[r].status << " free_energy "
+                      << signed_nan_like_reference(res[r].free_energy) << " overlap " << res[r].overlap << (r == best ? "  <- best" : "") << "\n";
+        for (unsigned q = 0; q < Q; ++q) std::cout << eta_out[size_t(best) * Q + q] << " ";  // output_vec(eta_)
+        std::cout << "\n";
+        for (unsigned r = 0; r < Q; ++r) {  // output_mat(cab_)
+            for (unsigned s = 0; s < Q; ++s) std::cout << cab_out[(size_t(best) * Q + r) * Q + s] << " ";
+            std::cout << "\n";
+        }
+        std::clog << "overlap:" << res[best].overlap << "\n";
+        stage("learning (all replicas)");
+        if (var_map.count("metrics_json")) {
+            const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            sbmbp_stats st;
+            sbmbp_batch_get_stats(bat, &st);
+            std::ofstream mj(var_map.get("metrics_json")[0].c_str());
+            auto jnum = [](double x) { std::ostringstream o; if (std::isfinite(x)) o << std::setprecision(17) << x; else o << "null"; return o.str(); };
+            mj << std::setprecision(12) << "{\"sweeps\":" << st.sweeps << ",\"edge_msg_updates\":" << st.edge_msg_updates
+               << ",\"marginal_gather_sweeps\":" << st.psi_form_sweeps << ",\"run_seconds\":" << secs
+               << ",\"bytes_per_sweep\":" << st.bytes_per_sweep << ",\"device_bytes\":" << st.device_bytes
+               << ",\"schedule\":\"jacobi\",\"learn_restarts\":" << R << ",\"best\":" << best;
+            auto arr = [&](const char *name, const std::vector<std::string> &vals) {
+                mj << ",\"" << name << "\":[";
+                for (size_t k = 0; k < vals.size(); ++k) mj << (k ? "," : "") << vals[k];
+                mj << "]";
+            };
+            std::vector<std::string> a_seed, a_steps, a_status, a_f, a_sw;
+            for (uint32_t r = 0; r < R; ++r) {
+                a_seed.push_back(std::to_string(seeds[r]));
+                a_steps.push_back(std::to_string(res[r].em_steps));
+                a_status.push_back(std::to_string(res[r].status));
+                a_f.push_back(jnum(res[r].free_energy));
+                a_sw.push_back(std::to_string(res[r].total_sweeps));
+            }
+            arr("seed", a_seed); arr("em_steps", a_steps); arr("status", a_status); arr("free_energy", a_f); arr("total_sweeps", a_sw);
             mj << "}\n";
         }
         sbmbp_batch_destroy(bat);

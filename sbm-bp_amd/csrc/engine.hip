@@ -1113,6 +1113,7 @@ int row_sums(sbmbp_engine *e, std::vector<double> &out /* 2Q + Q*Q */) {
     return SBMBP_OK;
 }
 
+void em_rescale(uint32_t Q, uint32_t N, uint32_t dc, const double *na, const double *nna, const double *tri, double *ce);
 int em_expect(sbmbp_engine *e, double *na_e, double *nna_e, double *cab_e) {
     if (!e->have_params || !e->have_state) { set_error("engine has no parameters or no state"); return SBMBP_ERR_STATE; }
     const uint32_t Q = e->Q;
@@ -1161,22 +1162,7 @@ int em_expect(sbmbp_engine *e, double *na_e, double *nna_e, double *cab_e) {
     CHK(fold_to_host(e, nb, T, T + 1, tri.data()));
     }
     std::vector<double> ce(Q * Q, 0.0);
-    uint32_t t = 0;
-    for (uint32_t q1 = 0; q1 < Q; ++q1)
-        for (uint32_t q2 = q1; q2 < Q; ++q2, ++t) { ce[q1 * Q + q2] = tri[t]; ce[q2 * Q + q1] = tri[t]; }
-    // rescaling of belief_propagation.cpp:967-988
-    const double EPS = 1.0e-50;
-    const double *nn = (e->dc == 0) ? na : nna;
-    for (uint32_t q1 = 0; q1 < Q; ++q1)
-        for (uint32_t q2 = q1; q2 < Q; ++q2)
-            if (na[q1] > EPS && na[q2] > EPS) {
-                if (q1 != q2) {
-                    ce[q1 * Q + q2] *= double(e->N) / (nn[q1] * nn[q2]);
-                    ce[q2 * Q + q1] = ce[q1 * Q + q2];
-                } else {
-                    ce[q1 * Q + q2] *= 2. * double(e->N) / (nn[q1] * nn[q2]);
-                }
-            }
+    em_rescale(Q, e->N, e->dc, na, nna, tri.data(), ce.data());
     if (na_e) std::copy(na, na + Q, na_e);
     if (nna_e) std::copy(nna, nna + Q, nna_e);
     if (cab_e) std::copy(ce.begin(), ce.end(), cab_e);
@@ -1236,6 +1222,54 @@ int overlap_impl(sbmbp_engine *e, double *ov, double *Cout) {
         *ov = best;
     }
     return SBMBP_OK;
+}
+
+// learning_step (bp.cpp:53-75) on the host, for the single engine and the replica batch alike.
+// bp.cpp:58-63 truncates lr*na_expect + (1-lr)*na to an integer. na_expect is a sum of N marginals, each known to
+// the BP criterion, so a value within snap = min(learn_snap * N * crit, 0.01) below an integer is that integer as
+// far as the fixed point is known (README run: 500 - 9e-5 with the relaxed field, 500 - 1.6e-7 without, on a
+// symmetric instance whose exact value is 500; the reference's own schedule happens to land at 500 + 4e-8).
+// Values further below an integer truncate exactly as in the reference.
+void learning_step_host(uint32_t Q, uint32_t N, double learning_rate, double learn_snap, double crit, const double *na_e,
+                        const double *cab_e, uint32_t *na, double *cab) {
+    uint32_t rest = N;
+    const double snap = std::min(learn_snap * double(N) * crit, 0.01);
+    for (uint32_t i = 0; i + 1 < Q; ++i) {
+        na[i] = unsigned(int(learning_rate * na_e[i] + (1.0 - learning_rate) * na[i] + snap));
+        rest -= na[i];
+    }
+    na[Q - 1] = rest;
+    for (uint32_t a = 0; a < Q * Q; ++a) cab[a] = learning_rate * cab_e[a] + (1.0 - learning_rate) * cab[a];
+}
+
+// which of n runs is best (sbmbp.h: sbmbp_best_replica)
+uint32_t best_replica(uint32_t n, const double *f, const int *rank, int n_ranks) {
+    int pick = -1;
+    for (int pass = 0; pass < n_ranks && pick < 0; ++pass)
+        for (uint32_t r = 0; r < n; ++r) {
+            if (rank[r] != pass || std::isnan(f[r])) continue;
+            if (pick < 0 || f[r] < f[pick]) pick = int(r);
+        }
+    return pick < 0 ? 0u : uint32_t(pick);
+}
+
+// cab_expect from the Q (Q + 1) / 2 numerators: symmetric fill and the rescaling of belief_propagation.cpp:967-988
+void em_rescale(uint32_t Q, uint32_t N, uint32_t dc, const double *na, const double *nna, const double *tri, double *ce) {
+    uint32_t t = 0;
+    for (uint32_t q1 = 0; q1 < Q; ++q1)
+        for (uint32_t q2 = q1; q2 < Q; ++q2, ++t) { ce[q1 * Q + q2] = tri[t]; ce[q2 * Q + q1] = tri[t]; }
+    const double EPS = 1.0e-50;
+    const double *nn = (dc == 0) ? na : nna;
+    for (uint32_t q1 = 0; q1 < Q; ++q1)
+        for (uint32_t q2 = q1; q2 < Q; ++q2)
+            if (na[q1] > EPS && na[q2] > EPS) {
+                if (q1 != q2) {
+                    ce[q1 * Q + q2] *= double(N) / (nn[q1] * nn[q2]);
+                    ce[q2 * Q + q1] = ce[q1 * Q + q2];
+                } else {
+                    ce[q1 * Q + q2] *= 2. * double(N) / (nn[q1] * nn[q2]);
+                }
+            }
 }
 
 void apply_params_host(sbmbp_engine *e, const double *cab, const uint32_t *na, double beta) {
@@ -1897,22 +1931,9 @@ int sbmbp_learning(sbmbp_engine_t *e, float learning_conv_crit, uint32_t learnin
         fold = fnew;
         if (std::isnan(fold) || std::isinf(fold)) { out->status = 2; break; }
         if (fdiff < learning_conv_crit) { out->status = 1; break; }
-        // learning_step (bp.cpp:53-75)
         std::vector<uint32_t> na(e->na);
-        uint32_t rest = e->N;
-        // bp.cpp:58-63 truncates lr*na_expect + (1-lr)*na to an integer. na_expect is a sum of N marginals, each known to
-        // the BP criterion, so a value within snap = min(learn_snap * N * crit, 0.01) below an integer is that integer as
-        // far as the fixed point is known (README run: 500 - 9e-5 with the relaxed field, 500 - 1.6e-7 without, on a
-        // symmetric instance whose exact value is 500; the reference's own schedule happens to land at 500 + 4e-8).
-        // Values further below an integer truncate exactly as in the reference.
-        const double snap = std::min(e->learn_snap * double(e->N) * double(learning_conv_crit), 0.01);
-        for (uint32_t i = 0; i + 1 < Q; ++i) {
-            na[i] = unsigned(int(learning_rate * na_e[i] + (1.0 - learning_rate) * na[i] + snap));
-            rest -= na[i];
-        }
-        na[Q - 1] = rest;
         std::vector<double> cab(e->cab);
-        for (uint32_t a = 0; a < Q * Q; ++a) cab[a] = learning_rate * cab_e[a] + (1.0 - learning_rate) * cab[a];
+        learning_step_host(Q, e->N, double(learning_rate), e->learn_snap, double(learning_conv_crit), na_e.data(), cab_e.data(), na.data(), cab.data());
         apply_params_host(e, cab.data(), na.data(), e->beta);
         out->em_steps++;
     }
@@ -2698,6 +2719,12 @@ struct sbmbp_batch {
     void *h_cs = nullptr;       // page-locked: two slots of R convergence states
     hipEvent_t ev_cs[2] = {nullptr, nullptr};
     uint64_t sweeps = 0;
+    // batched reductions of an EM step (batch_reductions): inputs [R][3 Q Q] matrices, then parities / mask / refresh mask
+    // as ints; partial tables; one result row per replica. The host sides are page-locked.
+    double *d_em_in = nullptr, *d_em_part[3] = {nullptr, nullptr, nullptr}, *d_em_res = nullptr;
+    size_t em_part_cap[3] = {0, 0, 0}, em_res_cap = 0;
+    void *h_em_in = nullptr, *h_em_res = nullptr;
+    size_t h_em_res_cap = 0;
 };
 
 namespace {
@@ -2780,21 +2807,34 @@ int batch_launch_sweep(sbmbp_batch *b, const batch_view &bv, uint32_t j, double 
 
 // run_sweeps for the batch: every replica starts from its current state, stops at its own sweep (device side, P[r].stop)
 // and keeps the state of that sweep; the call ends when all have stopped or after max_sweeps
-int batch_run(sbmbp_batch *b, double crit, uint32_t max_sweeps, double damping, int *niter, double *last) {
-    sbmbp_engine *e = b->e;
-    const uint32_t R = b->R;
-    for (uint32_t r = 0; r < R; ++r)
+// crit[r] is replica r's criterion. active (null = all): a replica that is not active is frozen: its parameter block is not
+// uploaded again, its stop flag is set, and its state and parity stay untouched; executed[r] (may be null) = sweeps replica
+// r executed in this call.
+int batch_check_ready(const sbmbp_batch *b, const char *what) {
+    for (uint32_t r = 0; r < b->R; ++r)
         if (!b->rep[r].have_params || !b->rep[r].have_state) {
-            set_error("set_params and init_messages/set_state must precede converge (replica " + std::to_string(r) + ")");
+            set_error(std::string("set_params and init_messages/set_state must precede ") + what + " (replica " + std::to_string(r) + ")");
             return SBMBP_ERR_STATE;
         }
+    return SBMBP_OK;
+}
+int batch_run(sbmbp_batch *b, const double *crit, const uint8_t *active, uint32_t max_sweeps, double damping, int *niter, double *last,
+              uint32_t *executed_out = nullptr) {
+    sbmbp_engine *e = b->e;
+    const uint32_t R = b->R;
+    CHK(batch_check_ready(b, "converge"));
     CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (e->Q + 1)));
     b->call_par.resize(R);
     for (uint32_t r = 0; r < R; ++r) {  // parameter block and initial field of every replica (once per call: a loop)
-        bound_replica v(b, r);
-        CHK(upload_params(e, crit, false));
-        CHK(launch_field(e, 1));
         b->call_par[r] = b->rep[r].par;
+        if (active && !active[r]) {
+            static const int one = 1;
+            HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(b->d_P + r) + offsetof(dev_params, stop), &one, sizeof(int), hipMemcpyHostToDevice, e->stream));
+            continue;
+        }
+        bound_replica v(b, r);
+        CHK(upload_params(e, crit[r], false));
+        CHK(launch_field(e, 1));
     }
     HIPCHK(hipMemcpyAsync(b->d_par, b->call_par.data(), size_t(R) * sizeof(int), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -2838,8 +2878,11 @@ int batch_run(sbmbp_batch *b, double crit, uint32_t max_sweeps, double damping, 
         }
     }
     for (uint32_t r = 0; r < R; ++r) {
+        if (executed_out) executed_out[r] = 0;
+        if (active && !active[r]) continue;  // frozen: P[r] still holds the records of its last run
         batch_replica &p = b->rep[r];
         const uint32_t executed = uint32_t(cs[r].sweep_idx);
+        if (executed_out) executed_out[r] = executed;
         p.par = (p.par + int(executed)) & 1;
         b->sweeps += executed;
         const bool relaxed = cs[r].ar_fl > 0 || cs[r].ar_gl >= 0;
@@ -2860,12 +2903,194 @@ void batch_free(sbmbp_batch *b) {
         b->e->d_M[0] = b->e->d_M[1] = b->e->d_psi[0] = b->e->d_psi[1] = nullptr;  // they pointed into the batch buffers
         b->e->d_P = nullptr;
     }
-    void *ptrs[] = {b->d_M, b->d_psi, b->d_rec, b->d_P, b->d_par, b->d_cs};
+    void *ptrs[] = {b->d_M, b->d_psi, b->d_rec, b->d_P, b->d_par, b->d_cs, b->d_em_in, b->d_em_part[0], b->d_em_part[1], b->d_em_part[2], b->d_em_res};
     for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (b->h_cs) (void)hipHostFree(b->h_cs);
+    void *hptrs[] = {b->h_cs, b->h_em_in, b->h_em_res};
+    for (void *p : hptrs) if (p) (void)hipHostFree(p);
     for (auto ev : b->ev_cs) if (ev) (void)hipEventDestroy(ev);
     if (b->e) sbmbp_destroy(b->e);
     delete b;
+}
+
+// device buffer of at least `need` doubles (grown, never shrunk)
+int batch_ensure(sbmbp_batch *b, double **p, size_t *cap, size_t need) {
+    if (need <= *cap) return SBMBP_OK;
+    if (*p) { (void)hipFree(*p); b->e->device_bytes -= *cap * 8; *p = nullptr; }
+    *cap = 0;
+    CHK(dev_alloc(b->e, p, need));
+    *cap = need;
+    return SBMBP_OK;
+}
+
+// The reductions of ONE EM step for every replica of the mask (null = all), from one launch sequence and one copy to the
+// host (kernels_batch.h): field refresh where the field is stale, frame pass (+ k_fe_hub per replica where the graph has
+// hub rows), the numerators' own kernel above EM_FRAME_QMAX labels, all-pairs non-edge term under dc 0 (exact or moment
+// series, as sbmbp_batch_set_nonedge_mode says), folds, ONE device-to-host copy, ONE synchronisation. The O(Q^2) host work
+// per replica (matrices of the non-edge term, contraction of the series, rescaling) stays a host loop.
+// Outputs (any may be null): na_e / nna_e [R][Q], cab_e [R][Q*Q], f [R], parts [R][3]. Rows of replicas outside the mask are
+// left untouched.
+int batch_reductions(sbmbp_batch *b, const uint8_t *mask, double *na_e, double *nna_e, double *cab_e, double *f, double *parts) {
+    sbmbp_engine *e = b->e;
+    const uint32_t R = b->R, Q = e->Q, N = e->N, QQ2 = Q * Q, T = Q * (Q + 1) / 2;
+    const uint32_t NP = uint32_t(em_np(int(Q)));
+    const bool em_in_frame = Q <= uint32_t(EM_FRAME_QMAX);
+    const bool nonedge = e->dc == 0, exact = nonedge && nonedge_exact(e);
+    const int adj_mode = nonedge ? (exact ? 2 : 1) : 0;
+
+    // ---- host: per-replica matrices, series order, masks -> one upload
+    const size_t in_doubles = size_t(R) * 3 * QQ2, in_bytes = in_doubles * 8 + size_t(3) * R * sizeof(int);
+    if (!b->h_em_in) {
+        HIPCHK(hipHostMalloc(&b->h_em_in, in_bytes, hipHostMallocDefault));
+        size_t cap = 0;
+        CHK(batch_ensure(b, &b->d_em_in, &cap, in_bytes / 8 + 1));
+    }
+    double *h_mats = static_cast<double *>(b->h_em_in);
+    int *h_par = reinterpret_cast<int *>(h_mats + in_doubles), *h_act = h_par + R, *h_ref = h_act + R;
+    const double *d_mats = b->d_em_in;
+    const int *d_par = reinterpret_cast<const int *>(b->d_em_in + in_doubles), *d_act = d_par + R, *d_ref = d_act + R;
+    std::vector<int> Kr(R, 0);
+    int K = 0;
+    bool any_refresh = false, any = false;
+    for (uint32_t r = 0; r < R; ++r) {
+        const batch_replica &p = b->rep[r];
+        const bool on = !mask || mask[r];
+        h_par[r] = p.par;
+        h_act[r] = on ? 1 : 0;
+        h_ref[r] = (on && !p.field_fresh) ? 1 : 0;
+        any = any || on;
+        any_refresh = any_refresh || h_ref[r];
+        double *wmat = h_mats + size_t(r) * 3 * QQ2, *Pmat = wmat + QQ2, *cabm = wmat + 2 * QQ2;
+        double wmax = 0.0;
+        for (uint32_t a = 0; a < QQ2; ++a) {  // (upload_nonedge_mats)
+            Pmat[a] = on ? std::pow(1.0 - p.cab[a] / double(N), p.beta) : 0.0;
+            wmat[a] = double(N) * (1.0 - Pmat[a]);
+            cabm[a] = on ? p.cab[a] : 0.0;
+            wmax = std::max(wmax, std::max(wmat[a], cabm[a]));
+        }
+        if (on && nonedge && !exact) { Kr[r] = choose_series_order(e, wmax); K = std::max(K, Kr[r]); }
+    }
+    if (!any) return SBMBP_OK;
+    uint32_t Tm = 0;
+    { uint32_t sz = 1; for (int k = 1; k <= K; ++k) { sz *= Q; Tm += sz; } }
+    const uint32_t n_all = nonedge ? (exact ? 1u : Tm) : 0u, RES = NP + n_all;
+
+    // ---- buffers
+    const uint32_t nbf = std::max<uint32_t>(1, (N + 4095) / 4096), rows = e->n_blk + e->n_hub;
+    const uint32_t nbe = uint32_t(std::min<uint64_t>(1024, std::max<uint64_t>(1, (e->E2 + BLOCK - 1) / BLOCK)));
+    const uint32_t g = (N + BLOCK - 1) / BLOCK, nbm = std::max<uint32_t>(1, (N + 511) / 512);
+    const size_t part0 = size_t(R) * std::max<size_t>(size_t(rows) * NP, size_t(nbf) * (Q + 1));  // field partials are folded before the frame pass writes
+    const size_t part1 = em_in_frame ? 0 : size_t(R) * nbe * T;
+    const size_t part2 = !nonedge ? 0 : (exact ? size_t(R) * g * g : size_t(R) * nbm * Tm);
+    CHK(batch_ensure(b, &b->d_em_part[0], &b->em_part_cap[0], part0));
+    if (part1) CHK(batch_ensure(b, &b->d_em_part[1], &b->em_part_cap[1], part1));
+    if (part2) CHK(batch_ensure(b, &b->d_em_part[2], &b->em_part_cap[2], part2));
+    CHK(batch_ensure(b, &b->d_em_res, &b->em_res_cap, size_t(R) * RES));
+    if (b->h_em_res_cap < size_t(R) * RES) {
+        if (b->h_em_res) { (void)hipHostFree(b->h_em_res); b->h_em_res = nullptr; b->h_em_res_cap = 0; }
+        HIPCHK(hipHostMalloc(&b->h_em_res, size_t(R) * RES * 8, hipHostMallocDefault));
+        b->h_em_res_cap = size_t(R) * RES;
+    }
+
+    // ---- device: one launch sequence for all replicas
+    hipStream_t st = e->stream;
+    HIPCHK(hipMemcpyAsync(b->d_em_in, b->h_em_in, in_bytes, hipMemcpyHostToDevice, st));
+    if (any_refresh) {  // the site terms read h of the current marginals (k_psi_sum + k_finalize mode 2)
+        DISPATCH_Q(Q, hipLaunchKernelGGL((k_psi_sum_batch<QQ>), dim3(nbf, R), dim3(BLOCK), 0, st, e->d_row_ptr, b->d_psi, d_par, d_ref, b->psi_stride,
+                                         R, N, 4096u, int(e->dc != 0), b->d_em_part[0]));
+        DISPATCH_Q(Q, hipLaunchKernelGGL((k_field_refresh_batch<QQ>), dim3(R), dim3(BLOCK), 0, st, b->d_P, d_ref, b->d_em_part[0], nbf));
+    }
+    const dim3 fgrid(e->n_blk, R);
+#define EM_FRAME(QV, DC2V, EMV, DCV)                                                                                                      \
+    hipLaunchKernelGGL((k_em_frame_batch<QV, DC2V, EMV>), fgrid, dim3(frame_cfg<QV>::TPB), 0, st, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg, \
+                       e->d_blk_row, e->d_blk_e0, b->d_M, b->d_psi, b->d_P, d_par, d_act, d_mats, b->msg_stride, b->psi_stride, R, DCV,    \
+                       adj_mode, rows, b->d_em_part[0])
+    if (e->dc == 2) {
+        DISPATCH_Q(Q, if (QQ <= EM_FRAME_QMAX) { EM_FRAME((QQ <= EM_FRAME_QMAX ? QQ : 2), true, true, 1); } else { EM_FRAME((QQ > EM_FRAME_QMAX ? QQ : 16), true, false, 1); });
+    } else {
+        DISPATCH_Q(Q, if (QQ <= EM_FRAME_QMAX) { EM_FRAME((QQ <= EM_FRAME_QMAX ? QQ : 2), false, true, int(e->dc)); } else { EM_FRAME((QQ > EM_FRAME_QMAX ? QQ : 16), false, false, int(e->dc)); });
+    }
+#undef EM_FRAME
+    if (e->n_hub)  // site and edge terms of the rows above a segment's capacity: k_fe_hub per replica on offset pointers
+        for (uint32_t r = 0; r < R; ++r) {
+            if (!h_act[r]) continue;
+            const double *M = b->d_M + (size_t(h_par[r]) * R + r) * b->msg_stride;
+            double *part = b->d_em_part[0] + size_t(r) * rows * NP;
+            if (e->dc == 2) {
+                DISPATCH_Q(Q, hipLaunchKernelGGL((k_fe_hub<QQ, true>), dim3(e->n_hub), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg, M,
+                                                 (const double *)nullptr, e->d_hub_row, e->d_hub_blk, b->d_P + r, 1, 0, part, NP, e->n_blk));
+            } else {
+                DISPATCH_Q(Q, hipLaunchKernelGGL((k_fe_hub<QQ, false>), dim3(e->n_hub), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg, M,
+                                                 (const double *)nullptr, e->d_hub_row, e->d_hub_blk, b->d_P + r, int(e->dc), 0, part, NP, e->n_blk));
+            }
+        }
+    auto fold = [&](const double *in, uint32_t n_rows, uint32_t cols, uint32_t off) {
+        hipLaunchKernelGGL(k_fold_batch, dim3((cols + BLOCK / 64 - 1) / (BLOCK / 64), R), dim3(BLOCK), 0, st, in, d_act, n_rows, cols, b->d_em_res, RES, off);
+    };
+    fold(b->d_em_part[0], rows, NP, 0);
+    if (!em_in_frame) {
+        if (e->dc == 2) {
+            DISPATCH_Q(Q, hipLaunchKernelGGL((k_em_edges_batch<(QQ > EM_FRAME_QMAX ? QQ : 16), true>), dim3(nbe, R), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev,
+                                             e->d_nbr, e->d_deg, e->d_src, b->d_M, b->d_P, d_par, d_act, b->msg_stride, R, uint32_t(e->E2), b->d_em_part[1]));
+        } else {
+            DISPATCH_Q(Q, hipLaunchKernelGGL((k_em_edges_batch<(QQ > EM_FRAME_QMAX ? QQ : 16), false>), dim3(nbe, R), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev,
+                                             e->d_nbr, e->d_deg, e->d_src, b->d_M, b->d_P, d_par, d_act, b->msg_stride, R, uint32_t(e->E2), b->d_em_part[1]));
+        }
+        fold(b->d_em_part[1], nbe, T, uint32_t(EM_NA) + 2 * Q);
+    }
+    if (nonedge && exact) {
+        DISPATCH_Q(Q, hipLaunchKernelGGL((k_nonedge_exact_batch<QQ>), dim3(g, g, R), dim3(BLOCK), 0, st, b->d_psi, d_par, d_act, d_mats, b->psi_stride, R, N,
+                                         b->d_em_part[2]));
+        fold(b->d_em_part[2], g * g, 1, NP);
+    } else if (nonedge && Tm) {
+        hipLaunchKernelGGL(k_moments_batch, dim3(nbm, R), dim3(BLOCK), 0, st, b->d_psi, d_par, d_act, b->psi_stride, R, N, int(Q), K, 512u, int(Tm),
+                           b->d_em_part[2]);
+        fold(b->d_em_part[2], nbm, Tm, NP);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(b->h_em_res, b->d_em_res, size_t(R) * RES * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));  // the round's one synchronisation
+
+    // ---- host: per replica
+    const double *res = static_cast<const double *>(b->h_em_res);
+    const double Nd = double(N);
+    std::vector<double> ce(QQ2);
+    for (uint32_t r = 0; r < R; ++r) {
+        if (!h_act[r]) continue;
+        batch_replica &p = b->rep[r];
+        if (h_ref[r]) p.field_fresh = true;
+        const double *row = res + size_t(r) * RES, *na = row + EM_NA, *nna = na + Q, *tri = nna + Q;
+        if (na_e) std::copy(na, na + Q, na_e + size_t(r) * Q);
+        if (nna_e) std::copy(nna, nna + Q, nna_e + size_t(r) * Q);
+        if (cab_e) {
+            em_rescale(Q, N, e->dc, na, nna, tri, ce.data());
+            std::copy(ce.begin(), ce.end(), cab_e + size_t(r) * QQ2);
+        }
+        if (f || parts) {  // (free_energy_impl, nonedge_terms)
+            double f_site = row[0] / Nd, f_edge = row[1] / (2.0 * Nd), f_non = 0.0;
+            if (e->dc == 1) { f_site += e->sum_log_didl / Nd; f_edge += e->sum_log_didl / (2.0 * Nd); }
+            if (nonedge) {
+                double all0 = 0.0;
+                if (exact) {
+                    all0 = row[NP];
+                } else {
+                    const double *wmat = h_mats + size_t(r) * 3 * QQ2;
+                    double Nk = 1.0;
+                    size_t off = 0, tsz = 1;
+                    for (int k = 1; k <= Kr[r]; ++k) {
+                        tsz *= Q;
+                        Nk *= Nd;
+                        std::vector<const double *> ms(k, wmat);
+                        all0 -= contract(row + NP + off, Q, unsigned(k), ms) / (double(k) * Nk);
+                        off += tsz;
+                    }
+                }
+                f_non = (all0 - row[EM_ADJ]) / (2.0 * Nd);
+            }
+            if (parts) { parts[3 * size_t(r)] = f_site; parts[3 * size_t(r) + 1] = f_edge; parts[3 * size_t(r) + 2] = f_non; }
+            if (f) f[r] = -f_site + f_edge + f_non;
+        }
+    }
+    return SBMBP_OK;
 }
 
 }  // namespace
@@ -3023,14 +3248,16 @@ int sbmbp_batch_sweep(sbmbp_batch_t *b, double damping, uint32_t n_sweeps, doubl
     device_scope dev_(b->e);
     const uint32_t keep = b->e->check_every;
     b->e->check_every = std::max<uint32_t>(keep, 64);  // no convergence test: sync rarely
-    const int r = batch_run(b, -1.0, n_sweeps, damping, nullptr, last);
+    const std::vector<double> crit(b->R, -1.0);
+    const int r = batch_run(b, crit.data(), nullptr, n_sweeps, damping, nullptr, last);
     b->e->check_every = keep;
     return r;
 }
 int sbmbp_batch_converge(sbmbp_batch_t *b, double crit, uint32_t max_sweeps, double damping, int *niter, double *last) {
     BATCH_ARGS(b);
     device_scope dev_(b->e);
-    return batch_run(b, crit, max_sweeps, damping, niter, last);
+    const std::vector<double> crits(b->R, crit);
+    return batch_run(b, crits.data(), nullptr, max_sweeps, damping, niter, last);
 }
 
 int sbmbp_batch_free_energy(sbmbp_batch_t *b, double *f, double *parts) {
@@ -3073,7 +3300,8 @@ int sbmbp_batch_inference(sbmbp_batch_t *b, float conv_crit, uint32_t time_conv,
     device_scope dev_(b->e);
     std::vector<int> niter(b->R);
     std::vector<double> last(b->R);
-    CHK(batch_run(b, double(conv_crit), time_conv, double(dumping_rate), niter.data(), last.data()));
+    const std::vector<double> crits(b->R, double(conv_crit));
+    CHK(batch_run(b, crits.data(), nullptr, time_conv, double(dumping_rate), niter.data(), last.data()));
     for (uint32_t r = 0; r < b->R; ++r) {
         bound_replica v(b, r);
         out[r].niter = niter[r];
@@ -3081,15 +3309,99 @@ int sbmbp_batch_inference(sbmbp_batch_t *b, float conv_crit, uint32_t time_conv,
         CHK(inference_reductions(b->e, &out[r]));
     }
     if (best) {  // lowest free energy among the converged replicas (among all when none converged); NaN never; ties: lowest index
-        int pick = -1;
-        for (int pass = 0; pass < 2 && pick < 0; ++pass)
-            for (uint32_t r = 0; r < b->R; ++r) {
-                if (pass == 0 && out[r].niter < 0) continue;
-                if (std::isnan(out[r].free_energy)) continue;
-                if (pick < 0 || out[r].free_energy < out[pick].free_energy) pick = int(r);
-            }
-        *best = pick < 0 ? 0u : uint32_t(pick);
+        std::vector<double> f(b->R);
+        std::vector<int> rank(b->R);
+        for (uint32_t r = 0; r < b->R; ++r) { f[r] = out[r].free_energy; rank[r] = out[r].niter >= 0 ? 0 : 1; }
+        *best = best_replica(b->R, f.data(), rank.data(), 2);
     }
+    return SBMBP_OK;
+}
+
+int sbmbp_batch_set_learning_schedule(sbmbp_batch_t *b, double field_mix, double snap) {
+    BATCH_ARGS(b);
+    return sbmbp_set_learning_schedule(b->e, field_mix, snap);
+}
+
+int sbmbp_batch_em_step(sbmbp_batch_t *b, double *na_expect, double *nna_expect, double *cab_expect, double *f, double *parts) {
+    BATCH_ARGS(b);
+    for (uint32_t r = 0; r < b->R; ++r)
+        if (!b->rep[r].have_params || !b->rep[r].have_state) {
+            set_error("replica " + std::to_string(r) + " has no parameters or no state");
+            return SBMBP_ERR_STATE;
+        }
+    device_scope dev_(b->e);
+    return batch_reductions(b, nullptr, na_expect, nna_expect, cab_expect, f, parts);
+}
+
+int sbmbp_batch_learning(sbmbp_batch_t *b, float learning_conv_crit, uint32_t learning_max_time, float learning_rate, float dumping_rate,
+                         sbmbp_learn_result *out, double *eta, double *cab, uint32_t *best) {
+    if (!b || !out) return arg_error(__func__, __LINE__);
+    CHK(batch_check_ready(b, "learning"));
+    sbmbp_engine *e = b->e;
+    device_scope dev_(e);
+    const uint32_t R = b->R, Q = e->Q;
+    // the relaxed field of the EM loop's BP runs (sbmbp_learning)
+    const double keep_mix = e->field_mix;
+    e->field_mix = std::min(e->field_mix, e->learn_field_mix);
+    struct restore { sbmbp_engine *e; double v; ~restore() { e->field_mix = v; } } restore_mix{e, keep_mix};
+    std::vector<float> crit(R, learning_conv_crit);
+    std::vector<double> critd(R), fold(R, 0.0), fdiff(R, 1.0), fnew(R), na_e(size_t(R) * Q), nna_e(size_t(R) * Q), cab_e(size_t(R) * Q * Q);
+    std::vector<uint8_t> active(R, 1);
+    std::vector<uint32_t> executed(R);
+    for (uint32_t r = 0; r < R; ++r) { out[r].em_steps = 0; out[r].status = 0; out[r].total_sweeps = 0; }
+    uint32_t n_active = R;
+    for (uint32_t t = 0; t < learning_max_time && n_active; ++t) {  // belief_propagation::learning (bp.cpp:27-47), all replicas in step
+        for (uint32_t r = 0; r < R; ++r) {
+            if (active[r] && fdiff[r] < crit[r]) crit[r] = float(double(crit[r]) * 0.1);
+            critd[r] = double(crit[r]);
+        }
+        CHK(batch_run(b, critd.data(), active.data(), learning_max_time, double(dumping_rate), nullptr, nullptr, executed.data()));
+        CHK(batch_reductions(b, active.data(), na_e.data(), nna_e.data(), cab_e.data(), fnew.data(), nullptr));
+        for (uint32_t r = 0; r < R; ++r) {
+            if (!active[r]) continue;
+            out[r].total_sweeps += executed[r];
+            fdiff[r] = std::fabs(fnew[r] - fold[r]);
+            fold[r] = fnew[r];
+            if (std::isnan(fold[r]) || std::isinf(fold[r])) out[r].status = 2;
+            else if (fdiff[r] < crit[r]) out[r].status = 1;
+            if (out[r].status) { active[r] = 0; --n_active; continue; }  // keeps the state and parameters of this round
+            std::vector<uint32_t> na(b->rep[r].na);
+            std::vector<double> cb(b->rep[r].cab);
+            learning_step_host(Q, e->N, double(learning_rate), e->learn_snap, double(crit[r]), na_e.data() + size_t(r) * Q,
+                               cab_e.data() + size_t(r) * Q * Q, na.data(), cb.data());
+            bound_replica v(b, r);
+            apply_params_host(e, cb.data(), na.data(), e->beta);
+            out[r].em_steps++;
+        }
+    }
+    std::vector<int> rank(R);
+    for (uint32_t r = 0; r < R; ++r) {
+        out[r].free_energy = fold[r];
+        rank[r] = out[r].status == 1 ? 0 : (out[r].status == 0 ? 1 : -1);
+        {
+            bound_replica v(b, r);
+            CHK(upload_params(e, 0.0));
+            e->field_fresh = false;  // (the parameter block starts from a zero field again)
+            CHK(overlap_impl(e, &out[r].overlap, nullptr));
+        }
+        const batch_replica &p = b->rep[r];
+        if (eta) std::copy(p.eta.begin(), p.eta.end(), eta + size_t(r) * Q);
+        if (cab) std::copy(p.cab.begin(), p.cab.end(), cab + size_t(r) * Q * Q);
+    }
+    if (best) *best = best_replica(R, fold.data(), rank.data(), 2);
+    return SBMBP_OK;
+}
+
+int sbmbp_learning_step_host(uint32_t Q, uint32_t n_vertices, double learning_rate, double snap, double crit, const double *na_expect,
+                             const double *cab_expect, uint32_t *na, double *cab) {
+    if (Q < 1 || !na_expect || !cab_expect || !na || !cab) return arg_error(__func__, __LINE__);
+    learning_step_host(Q, n_vertices, learning_rate, snap, crit, na_expect, cab_expect, na, cab);
+    return SBMBP_OK;
+}
+
+int sbmbp_best_replica(uint32_t n, const double *free_energy, const int *rank, int n_ranks, uint32_t *best) {
+    if (!n || !free_energy || !rank || !best) return arg_error(__func__, __LINE__);
+    *best = best_replica(n, free_energy, rank, n_ranks);
     return SBMBP_OK;
 }
 

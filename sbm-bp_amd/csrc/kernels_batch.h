@@ -262,5 +262,410 @@ k_batch_conv_states(const dev_params *__restrict__ P, uint32_t R, uint32_t off, 
     }
 }
 
+// ================================================================================================
+// The reductions of one EM step for all replicas (sbmbp_batch_em_step, sbmbp_batch_learning): the replica is a grid
+// dimension of every kernel, `active` [R] says which replicas take part (a mask argument, not the stop flag: a replica that
+// has stopped SWEEPING is exactly the one whose reductions are wanted). A replica that is not active returns before any
+// barrier. The state of replica r is the buffer par[r] (the host's parity, uploaded with the mask).
+// ================================================================================================
+
+// field refresh (k_psi_sum + k_finalize mode 2): chunk blockIdx.x of replica blockIdx.y -> partials[r][chunk][Q + 1]
+template <int Q>
+__global__ void __launch_bounds__(BLOCK)
+k_psi_sum_batch(const uint32_t *__restrict__ row_ptr, const double *__restrict__ psi_all, const int *__restrict__ par_all,
+                const int *__restrict__ active, size_t psi_stride, uint32_t R, uint32_t n_rows, uint32_t rows_per_blk, int dc,
+                double *__restrict__ partials) {
+    const uint32_t rep = blockIdx.y;
+    if (!active[rep]) return;
+    __shared__ double sred[4 * (Q + 1)];
+    const double *__restrict__ psi = psi_all + (size_t(par_all[rep]) * R + rep) * psi_stride;
+    double S[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) S[q] = 0.0;
+    const uint32_t lo = blockIdx.x * rows_per_blk;
+    const uint32_t hi = min(n_rows, lo + rows_per_blk);
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += BLOCK) {
+        double pv[Q];
+        load_vec<Q>(psi + size_t(i) * Q, pv);
+        const double gi = dc ? double(row_ptr[i + 1] - row_ptr[i]) : 1.0;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) S[q] += gi * pv[q];
+    }
+    block_reduce_store<Q>(S, 0.0, sred, partials + (size_t(rep) * gridDim.x + blockIdx.x) * (Q + 1));
+}
+// workgroup r: fold of replica r's chunks in a fixed order, then the exact field of P[r] (finalize_update mode 2)
+template <int Q>
+__global__ void __launch_bounds__(BLOCK)
+k_field_refresh_batch(dev_params *__restrict__ Pall, const int *__restrict__ active, const double *__restrict__ partials, uint32_t n_part) {
+    if (!active[blockIdx.x]) return;
+    dev_params *__restrict__ P = Pall + blockIdx.x;
+    __shared__ double sacc[(BLOCK / 64) * (Q + 1)];
+    __shared__ double sout[Q + 1];
+    __shared__ double s_hN[Q];
+    fold_rows<Q, false>(partials + size_t(blockIdx.x) * n_part * (Q + 1), 0, n_part, sacc, sout);
+    if (threadIdx.x == 0) finalize_update<Q>(P, sout, 2, nullptr, 0u, 0, s_hN);
+    __syncthreads();
+    field_table<Q>(P, s_hN);
+}
+
+// block sums of NS lane values -> out[0 .. NS) (no max slot), fixed order; sred holds NW * NS doubles and is free again
+// after the closing barrier
+template <int NS, int NW> __device__ __forceinline__ void block_sum_store(double (&s)[NS], double *sred, double *out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < NS; ++q) s[q] = wave_sum(s[q]);
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < NS; ++q) sred[wave * NS + q] = s[q];
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < NS; q += NW * 64) {
+        double a = sred[q];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) a += sred[w * NS + q];
+        out[q] = a;
+    }
+    __syncthreads();
+}
+
+// Record of the batched frame pass, EM_NP(Q) doubles per segment (and per hub row behind the segments: k_fe_hub fills the
+// FE_NP + 1 leading slots of those and zeroes the rest):
+//   [0] sum log Z_i   [1] sum log(m_in^T W m_out)   [2..4] unused (entropy terms and max slot of k_fe_hub's record)
+//   [5] adjacent pairs of the non-edge term (dc 0)   [6 .. 6+Q) na_expect   [6+Q .. 6+2Q) nna_expect   then Q(Q+1)/2 EM numerators
+constexpr int EM_ADJ = FE_NP + 1, EM_NA = FE_NP + 2;
+__host__ __device__ constexpr int em_np(int Q) { return EM_NA + 2 * Q + Q * (Q + 1) / 2; }
+// the EM numerators stay in the frame pass up to this label count (Q (Q + 1) / 2 accumulators and as many terms per lane:
+// tools/kernel_resources.py); above it k_em_edges_batch computes them
+constexpr int EM_FRAME_QMAX = 8;
+
+// per directed edge: EM numerators of k_em_edges
+template <int Q, bool DC2>
+__device__ __forceinline__ void em_edge_terms(const dev_params *__restrict__ P, const double (&mi)[Q], const double (&mo)[Q], double didl,
+                                              double (&acc)[Q * (Q + 1) / 2]) {
+    constexpr int T = Q * (Q + 1) / 2;
+    double term[T], norm_L = 0.0;
+    int t = 0;
+#pragma unroll
+    for (int q1 = 0; q1 < Q; ++q1) {
+#pragma unroll
+        for (int q2 = q1; q2 < Q; ++q2, ++t) {
+            double w = P->cab[q1 * Q + q2];
+            if (DC2) { double x = didl * w * P->invN; w = x / (1.0 + x); }
+            const double pr = (q1 == q2) ? (mi[q1] * mo[q2]) : (mi[q1] * mo[q2] + mi[q2] * mo[q1]);
+            term[t] = w * pr;
+            norm_L += term[t];
+        }
+    }
+    const double inv = 0.5 / norm_L;
+#pragma unroll
+    for (int u = 0; u < T; ++u) acc[u] += term[u] * inv;
+}
+// per directed edge (i, l): adjacent-pair term of the non-edge sum. adj_mode 1: series form (k_nonedge_adj, mat = N (1 -
+// (1 - cab/N)^beta)); 2: exact form (k_nonedge_exact_adj, mat = (1 - cab/N)^beta)
+template <int Q>
+__device__ __forceinline__ double adj_pair_term(const double *__restrict__ psi, uint32_t i, uint32_t l, const double *__restrict__ mat,
+                                                double invN, int adj_mode) {
+    double pi[Q], pl[Q];
+    load_vec<Q>(psi + size_t(i) * Q, pi);
+    load_vec<Q>(psi + size_t(l) * Q, pl);
+    double y = 0.0;
+#pragma unroll
+    for (int q1 = 0; q1 < Q; ++q1) {
+#pragma unroll
+        for (int q2 = 0; q2 < Q; ++q2) y += mat[q1 * Q + q2] * (pi[q1] * pl[q2]);
+    }
+    if (adj_mode == 1) return log1p(-y * invN);
+    return y != 0.0 ? log(y) : 0.0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// K3b: frame pass of the EM step over segment blockIdx.x of replica blockIdx.y: k_fe_frame's site and edge terms of the
+// free energy, the adjacent pairs of the non-edge term (dc 0), the row sums na_expect / nna_expect and, with EM, the
+// numerators of cab_expect. The numerators leave the registers (block_sum_store) before the lane-per-row phase starts, so
+// they are never live together with the row sums.
+// A hub row (a segment above CAP edges) has its site and edge terms from k_fe_hub; here its edges are walked by the whole
+// workgroup for the adjacent pairs and the numerators, and lane 0 adds its row sums.
+// ------------------------------------------------------------------------------------------------
+template <int Q, bool DC2, bool EM>
+__global__ void __launch_bounds__(frame_cfg<Q>::TPB)
+k_em_frame_batch(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ rev, const uint32_t *__restrict__ nbr,
+                 const uint32_t *__restrict__ ndeg, const uint32_t *__restrict__ blk_row, const uint32_t *__restrict__ blk_e0,
+                 const double *__restrict__ Mall, const double *__restrict__ psi_all, const dev_params *__restrict__ Pall,
+                 const int *__restrict__ par_all, const int *__restrict__ active, const double *__restrict__ mats_all /* [R][3 Q Q] */,
+                 size_t msg_stride, size_t psi_stride, uint32_t R, int dc, int adj_mode, uint32_t rec_rows /* records per replica */,
+                 double *__restrict__ partials) {
+    constexpr int EPT = frame_cfg<Q>::EPT, CAP = frame_cfg<Q>::CAP, RCAP = frame_cfg<Q>::RCAP, TPB = frame_cfg<Q>::TPB, NW = frame_cfg<Q>::WAVES;
+    constexpr int T = Q * (Q + 1) / 2, NP = em_np(Q), NRED = (EM && T > 2 * Q) ? T : 2 * Q;
+    const uint32_t rep = blockIdx.y;
+    if (!active[rep]) return;  // uniform, before any barrier
+    __shared__ double sb[CAP * Q];
+    __shared__ uint32_t srp[RCAP + 1];
+    __shared__ uint16_t srow[CAP];
+    __shared__ double sred[NW * NRED];
+    __shared__ double ssc[3];
+    const int tid = threadIdx.x;
+    const dev_params *__restrict__ P = Pall + rep;
+    const int par = par_all[rep];
+    const double *__restrict__ M = Mall + (size_t(par) * R + rep) * msg_stride;
+    const double *__restrict__ psi = psi_all + (size_t(par) * R + rep) * psi_stride;
+    const double *__restrict__ mat = mats_all + size_t(rep) * 3 * Q * Q + (adj_mode == 2 ? Q * Q : 0);
+    const double invN = P->invN;
+    const uint32_t r0 = blk_row[blockIdx.x], r1 = blk_row[blockIdx.x + 1];
+    const int nrows = int(r1 - r0);
+    const uint32_t e0 = blk_e0[blockIdx.x];
+    const int ne = int(blk_e0[blockIdx.x + 1] - e0);
+    double *__restrict__ rec = partials + (size_t(rep) * rec_rows + blockIdx.x) * NP;
+    double f_site = 0.0, f_edge = 0.0, f_adj = 0.0;
+    double tri[T];  // the numerators (lane-per-edge phase; dead without EM)
+#pragma unroll
+    for (int u = 0; u < T; ++u) tri[u] = 0.0;
+    double rs[2 * Q];  // na_expect, nna_expect (lane-per-row phase)
+#pragma unroll
+    for (int x = 0; x < 2 * Q; ++x) rs[x] = 0.0;
+    if (ne > CAP) {  // hub row (uniform)
+        const double di = double(ne);
+        for (int le = tid; le < ne; le += TPB) {
+            const uint32_t k = e0 + uint32_t(le);
+            if (EM) {
+                double mi[Q], mo[Q];
+                load_msg<Q>(M, size_t(rev[k]), mi);
+                load_msg<Q>(M, size_t(k), mo);
+                em_edge_terms<Q, DC2>(P, mi, mo, DC2 ? di * double(ndeg[nbr[k]]) : 0.0, tri);
+            }
+            if (adj_mode) f_adj += adj_pair_term<Q>(psi, r0, nbr[k], mat, invN, adj_mode);
+        }
+        if (tid == 0) {
+            double pv[Q];
+            load_vec<Q>(psi + size_t(r0) * Q, pv);
+#pragma unroll
+            for (int q = 0; q < Q; ++q) { rs[q] = pv[q]; rs[Q + q] = di * pv[q]; }
+        }
+    } else {
+        constexpr int RPT = RCAP / TPB + 1;
+        uint32_t kk[EPT], rk[EPT], rpv[RPT];
+        double mo_[EPT][Q], mi_[EPT][Q];
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) {
+            const int le = j * TPB + tid;
+            kk[j] = (ne > 0) ? e0 + uint32_t(le < ne ? le : 0) : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) rk[j] = rev[kk[j]];
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) load_msg<Q>(M, size_t(kk[j]), mo_[j]);
+#pragma unroll
+        for (int t = 0; t < RPT; ++t) { const int r = tid + t * TPB; rpv[t] = row_ptr[r0 + uint32_t(r < nrows ? r : nrows)]; }
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) load_msg<Q>(M, size_t(rk[j]), mi_[j]);
+#pragma unroll
+        for (int t = 0; t < RPT; ++t) { const int r = tid + t * TPB; if (r <= nrows) srp[r] = rpv[t] - e0; }
+        __syncthreads();
+        if (DC2 || adj_mode) {  // uniform: per-edge weights and the adjacent pairs need the edge -> row map
+            for (int r = tid; r < nrows; r += TPB)
+                for (int e = int(srp[r]); e < int(srp[r + 1]); ++e) srow[e] = uint16_t(r);
+            __syncthreads();
+        }
+#pragma unroll
+        for (int j = 0; j < EPT; ++j) {
+            const int le = j * TPB + tid;
+            if (le < ne) {
+                double (&mi)[Q] = mi_[j];
+                double (&mo)[Q] = mo_[j];
+                double b[Q];
+                double didl = 0.0;
+                if (DC2) {
+                    const int r = srow[le];
+                    didl = double(srp[r + 1] - srp[r]) * double(ndeg[nbr[e0 + le]]);
+                }
+                edge_field<Q, DC2>(P, mi, didl, b);
+                store_vec<Q>(&sb[le * Q], b);
+                double ln, en;
+                edge_terms<Q, DC2>(P, mi, mo, didl, 0, ln, en);
+                f_edge += ln;
+                if (EM) em_edge_terms<Q, DC2>(P, mi, mo, didl, tri);
+                if (adj_mode) f_adj += adj_pair_term<Q>(psi, r0 + uint32_t(srow[le]), nbr[e0 + le], mat, invN, adj_mode);
+            }
+        }
+    }
+    // the lane-per-edge sums leave the registers here (the barriers inside also complete sb)
+    if (EM) {
+        block_sum_store<T, NW>(tri, sred, rec + EM_NA + 2 * Q);
+    } else {
+        for (int u = tid; u < T; u += TPB) rec[EM_NA + 2 * Q + u] = 0.0;  // k_em_edges_batch has them
+        __syncthreads();
+    }
+    if (ne <= CAP) {  // uniform
+        for (int r = tid; r < nrows; r += TPB) {
+            const int es = int(srp[r]), ee = int(srp[r + 1]);
+            const double di = double(ee - es);
+            double A[Q];
+            int ae[Q];
+#pragma unroll
+            for (int q = 0; q < Q; ++q) { A[q] = 1.0; ae[q] = 0; }
+            for (int e = es; e < ee; ++e) {
+#pragma unroll
+                for (int q = 0; q < Q; ++q) A[q] *= sb[e * Q + q];
+                if (((e - es) & 7) == 7) x_norm<Q>(A, ae);
+            }
+            x_norm<Q>(A, ae);
+            f_site += log_partition_x<Q>(P, dc, di, A, ae);
+            double pv[Q];
+            load_vec<Q>(psi + size_t(r0 + r) * Q, pv);
+#pragma unroll
+            for (int q = 0; q < Q; ++q) { rs[q] += pv[q]; rs[Q + q] += di * pv[q]; }
+        }
+    }
+    block_sum_store<2 * Q, NW>(rs, sred, rec + EM_NA);
+    double sc[3] = {f_site, f_edge, f_adj};
+    block_sum_store<3, NW>(sc, sred, ssc);
+    if (tid == 0) {
+        rec[0] = ssc[0]; rec[1] = ssc[1]; rec[2] = 0.0; rec[3] = 0.0; rec[4] = 0.0;
+        rec[EM_ADJ] = ssc[2];
+    }
+}
+
+// K5b: the EM numerators of k_em_edges for replica blockIdx.y (label counts above EM_FRAME_QMAX): grid-stride over the
+// directed edges, partials[r][blockIdx.x][T]
+template <int Q, bool DC2>
+__global__ void __launch_bounds__(BLOCK)
+k_em_edges_batch(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ rev, const uint32_t *__restrict__ nbr,
+                 const uint32_t *__restrict__ ndeg, const uint32_t *__restrict__ src, const double *__restrict__ Mall,
+                 const dev_params *__restrict__ Pall, const int *__restrict__ par_all, const int *__restrict__ active, size_t msg_stride,
+                 uint32_t R, uint32_t n_edges, double *__restrict__ partials) {
+    constexpr int T = Q * (Q + 1) / 2;
+    const uint32_t rep = blockIdx.y;
+    if (!active[rep]) return;
+    __shared__ double sred[4 * T];
+    const dev_params *__restrict__ P = Pall + rep;
+    const double *__restrict__ M = Mall + (size_t(par_all[rep]) * R + rep) * msg_stride;
+    double acc[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) acc[t] = 0.0;
+    for (uint32_t k = blockIdx.x * BLOCK + threadIdx.x; k < n_edges; k += gridDim.x * BLOCK) {
+        double mi[Q], mo[Q];
+        load_msg<Q>(M, size_t(rev[k]), mi);
+        load_msg<Q>(M, size_t(k), mo);
+        double didl = 0.0;
+        if (DC2) {
+            const uint32_t i = src[k], l = nbr[k];
+            didl = double(row_ptr[i + 1] - row_ptr[i]) * double(ndeg[l]);
+        }
+        em_edge_terms<Q, DC2>(P, mi, mo, didl, acc);
+    }
+    block_sum_store<T, 4>(acc, sred, partials + (size_t(rep) * gridDim.x + blockIdx.x) * T);
+}
+
+// K4b with the replica as blockIdx.y: moment tensors of replica r's marginals, partials[r][blockIdx.x][T] (k_moments)
+__global__ void __launch_bounds__(BLOCK)
+k_moments_batch(const double *__restrict__ psi_all, const int *__restrict__ par_all, const int *__restrict__ active, size_t psi_stride,
+                uint32_t R, uint32_t n_rows, int Q, int K, uint32_t rows_per_blk, int T, double *__restrict__ partials) {
+    const uint32_t rep = blockIdx.y;
+    if (!active[rep]) return;
+    __shared__ double sp[BLOCK * QMAX];
+    __shared__ double scomb[BLOCK];
+    const double *__restrict__ psi = psi_all + (size_t(par_all[rep]) * R + rep) * psi_stride;
+    double *__restrict__ out = partials + (size_t(rep) * gridDim.x + blockIdx.x) * T;
+    const int tid = threadIdx.x;
+    constexpr int MAXE = 20;  // entries per thread (k_moments)
+    double acc[MAXE];
+    for (int j = 0; j < MAXE; ++j) acc[j] = 0.0;
+    const int nsub = T < BLOCK / 2 ? BLOCK / T : 1;
+    const int sub = nsub > 1 ? tid / T : 0;
+    const bool own = nsub == 1 || tid < nsub * T;
+    const uint32_t lo = blockIdx.x * rows_per_blk, hi = min(n_rows, lo + rows_per_blk);
+    for (uint32_t base = lo; base < hi; base += BLOCK) {
+        const uint32_t cnt = min(uint32_t(BLOCK), hi - base);
+        __syncthreads();
+        for (uint32_t x = tid; x < cnt * Q; x += BLOCK) sp[x] = psi[size_t(base) * Q + x];
+        __syncthreads();
+        int j = 0;
+        for (int ent = nsub > 1 ? tid % T : tid; own && ent < T; ent += BLOCK, ++j) {
+            int k = 1, off = 0, sz = Q;
+            while (ent >= off + sz) { off += sz; sz *= Q; ++k; }
+            int idx = ent - off;
+            int a[4];
+            for (int t = 0; t < 4; ++t) { a[t] = idx % Q; idx /= Q; }
+            double s = 0.0;
+            for (uint32_t r = uint32_t(sub); r < cnt; r += uint32_t(nsub)) {
+                const double *p = &sp[r * Q];
+                double v = p[a[0]];
+                if (k > 1) v *= p[a[1]];
+                if (k > 2) v *= p[a[2]];
+                if (k > 3) v *= p[a[3]];
+                s += v;
+            }
+            acc[j] += s;
+        }
+    }
+    if (nsub > 1) {  // combine the sub-sums of an entry in a fixed order
+        __syncthreads();
+        scomb[tid] = own ? acc[0] : 0.0;
+        __syncthreads();
+        if (tid < T) {
+            double s = scomb[tid];
+            for (int u = 1; u < nsub; ++u) s += scomb[u * T + tid];
+            out[tid] = s;
+        }
+        return;
+    }
+    int j = 0;
+    for (int ent = tid; ent < T; ent += BLOCK, ++j) out[ent] = acc[j];
+}
+
+// K4x with the replica as blockIdx.z: log(psi_i^T P_r psi_l) over all ordered pairs of replica r (k_nonedge_exact without
+// the entropy term), partials[r][blockIdx.y * gridDim.x + blockIdx.x]
+template <int Q>
+__global__ void __launch_bounds__(BLOCK)
+k_nonedge_exact_batch(const double *__restrict__ psi_all, const int *__restrict__ par_all, const int *__restrict__ active,
+                      const double *__restrict__ mats_all /* [R][3 Q Q]; P_r is the second matrix */, size_t psi_stride, uint32_t R,
+                      uint32_t n, double *__restrict__ partials) {
+    const uint32_t rep = blockIdx.z;
+    if (!active[rep]) return;
+    __shared__ double sl[BLOCK * Q];
+    __shared__ double sred[4];
+    const double *__restrict__ psi = psi_all + (size_t(par_all[rep]) * R + rep) * psi_stride;
+    const double *__restrict__ Pmat = mats_all + size_t(rep) * 3 * Q * Q + Q * Q;
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    const uint32_t l0 = blockIdx.y * BLOCK;
+    const uint32_t cnt = min(uint32_t(BLOCK), n - l0);
+    for (uint32_t x = threadIdx.x; x < cnt * Q; x += BLOCK) sl[x] = psi[size_t(l0) * Q + x];
+    __syncthreads();
+    double acc[1] = {0.0};
+    if (i < n) {
+        double pi[Q], v[Q];
+        load_vec<Q>(psi + size_t(i) * Q, pi);
+#pragma unroll
+        for (int q2 = 0; q2 < Q; ++q2) {
+            double a = 0.0;
+#pragma unroll
+            for (int q1 = 0; q1 < Q; ++q1) a += Pmat[q1 * Q + q2] * pi[q1];
+            v[q2] = a;
+        }
+        for (uint32_t r = 0; r < cnt; ++r) {
+            double f = 0.0;
+#pragma unroll
+            for (int q = 0; q < Q; ++q) f += v[q] * sl[r * Q + q];
+            if (f != 0.0) acc[0] += log(f);
+        }
+    }
+    block_sum_store<1, 4>(acc, sred, partials + size_t(rep) * gridDim.x * gridDim.y + size_t(blockIdx.y) * gridDim.x + blockIdx.x);
+}
+
+// fold of [R][rows][cols] partials to out[r * out_stride + out_off + c], c < cols: replica blockIdx.y, one wave per column
+// (lanes stride the rows, then the fixed shuffle tree of wave_sum): the order depends on nothing but the shape
+__global__ void __launch_bounds__(BLOCK)
+k_fold_batch(const double *__restrict__ in, const int *__restrict__ active, uint32_t rows, uint32_t cols, double *__restrict__ out,
+             uint32_t out_stride, uint32_t out_off) {
+    const uint32_t rep = blockIdx.y;
+    if (!active[rep]) return;
+    const uint32_t c = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+    if (c >= cols) return;  // wave-uniform; no barrier below
+    const double *__restrict__ p = in + size_t(rep) * rows * cols + c;
+    double a = 0.0;
+    for (uint32_t r = threadIdx.x & 63; r < rows; r += 64) a += p[size_t(r) * cols];
+    a = wave_sum(a);
+    if ((threadIdx.x & 63) == 0) out[size_t(rep) * out_stride + out_off + c] = a;
+}
+
 }  // namespace sbmbp
 #endif
