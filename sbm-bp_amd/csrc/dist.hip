@@ -24,6 +24,7 @@
 
 #include "../../include/sbmbp.h"
 #include "host_graph.h"
+#include "host_loops.h"
 
 using sbmbp::set_error;
 using sbmbp::arg_error;
@@ -843,59 +844,21 @@ int run(sbmbp_dist *d, double crit, u32 max_sweeps, double damping, int *niter, 
     const bool first_explicit = !d->consistent && !first_from_psi;
     CHK(sbmbp_set_schedule(d->eng, d->field_mix, 1));
     CHK(begin_run(d, crit, psi_ok, psi_ok && !first_explicit));
-    u32 done = 0;
     sbmbp_conv_state cs{0.0, -1, 0, 0, 1, 0, 0, -1};
-    // batch sizes follow the decay of the reported difference (as run_sweeps of the single engine does): identical on every
-    // rank, because the state they are computed from is
-    const u32 batch_max = std::max<u32>(1, d->check_every);
-    u32 next_batch = batch_max;
-    double prev_md = -1.0;
-    int prev_idx = 0;
-    auto plan_next = [&](const sbmbp_conv_state &st) {
-        if (crit > 0 && prev_md > 0 && st.maxdiff > 0 && st.maxdiff < prev_md && st.sweep_idx > prev_idx) {
-            const double rate = std::pow(st.maxdiff / prev_md, 1.0 / double(st.sweep_idx - prev_idx));
-            const double need = st.maxdiff > crit ? std::ceil(std::log(crit / st.maxdiff) / std::log(rate)) : 1.0;
-            const double ahead = double(done) - double(st.sweep_idx);
-            next_batch = u32(std::min<double>(batch_max, std::max(1.0, need - ahead)));
-        } else {
-            next_batch = batch_max;
-        }
-        if (st.maxdiff > 0) { prev_md = st.maxdiff; prev_idx = st.sweep_idx; }
-    };
-    bool form_psi = psi_ok;  // adaptive relaxation can ask for damping in the middle of a run (sbmbp_conv_state::pause): every
-                             // rank sees the same state, so all switch to the message-gather form on the same sweep
+    // planned batches and the pause (adaptive relaxation asking for damping in the middle of a run) as in run_sweeps of the
+    // single engine: identical on every rank, because the state they are computed from is
+    sbmbp::batch_planner plan(std::max<u32>(1, d->check_every), crit);
     u32 psi_count = 0;
-    auto queue_batch = [&](int slot) -> int {
-        const u32 batch = std::min(next_batch, max_sweeps - done);
-        for (u32 b = 0; b < batch; ++b) {
-            const u32 j = done + b;
+    auto queue_batch = [&](int slot, u32 first, u32 n, bool form_psi) -> int {
+        for (u32 j = first; j < first + n; ++j) {
             if (form_psi && !(j == 0 && first_explicit)) CHK(queue_sweep_psi(d, j));
             else CHK(queue_sweep_explicit(d, j, damping, form_psi));
         }
-        done += batch;
         return sbmbp_shard_state_record(d->eng, slot);
     };
-    while (done < max_sweeps) {
-        const u32 start = done;
-        CHK(queue_batch(0));
-        for (int k = 0;; ++k) {
-            const bool more = done < max_sweeps;
-            if (more) CHK(queue_batch((k + 1) & 1));
-            CHK(sbmbp_shard_state_wait(d->eng, k & 1, &cs));
-            plan_next(cs);
-            if (cs.stop || !more) {
-                if (more) CHK(sbmbp_shard_state_wait(d->eng, (k + 1) & 1, &cs));  // drain the batch queued ahead (no-ops after a stop)
-                break;
-            }
-        }
-        if (form_psi) psi_count += u32(cs.sweep_idx) - start - ((first_explicit && start == 0 && cs.sweep_idx > 0) ? 1 : 0);
-        if (!(cs.stop && cs.pause)) break;
-        done = u32(cs.sweep_idx);
-        form_psi = false;
-        CHK(sbmbp_shard_resume(d->eng));
-        next_batch = batch_max;
-        prev_md = -1.0;
-    }
+    CHK(sbmbp::converge_run(max_sweeps, plan, psi_ok, first_explicit, queue_batch,
+                     [&](int slot, sbmbp_conv_state *st) { return sbmbp_shard_state_wait(d->eng, slot, st); },
+                     [&]() { return sbmbp_shard_resume(d->eng); }, &cs, &psi_count));
     HIPCHK(hipStreamSynchronize(d->s_comm));
     for (auto sx : d->s_aux) HIPCHK(hipStreamSynchronize(sx));
     HIPCHK(hipStreamSynchronize(d->s_compute));
@@ -1384,45 +1347,33 @@ int sbmbp_dist_learning(sbmbp_dist_t *d, float learning_conv_crit, uint32_t lear
     if (!d || !out) return arg_error(__func__, __LINE__);
     device_guard guard(d->device);
     if (!d->have_params || !d->have_state) { set_error("set_params and an initial state must precede learning"); return SBMBP_ERR_STATE; }
-    const u32 Q = d->Q, N = d->plan.n_global;
-    std::vector<double> na_e(Q), nna_e(Q), cab_e(size_t(Q) * Q);
-    double fold = 0.0, fdiff = 1.0;
-    // the two rules of the synchronous EM loop (sbmbp_set_learning_schedule; DESIGN.md section 2), as sbmbp_learning
-    const double keep_mix = d->field_mix;
-    d->field_mix = std::min(d->field_mix, d->learn_field_mix);
-    struct restore { sbmbp_dist *d; double v; ~restore() { d->field_mix = v; } } restore_mix{d, keep_mix};
-    out->em_steps = 0;
-    out->status = 0;
-    const u64 sweeps0 = d->total_sweeps;
-    for (u32 t = 0; t < learning_max_time; ++t) {  // belief_propagation::learning (bp.cpp:27-47)
-        if (fdiff < learning_conv_crit) learning_conv_crit = float(double(learning_conv_crit) * 0.1);
-        int niter;
-        double last;
-        CHK(run(d, double(learning_conv_crit), learning_max_time, double(dumping_rate), &niter, &last));
-        CHK(em_expect(d, na_e.data(), nna_e.data(), cab_e.data()));
-        double tt[6];
-        CHK(fe_terms(d, false, tt));
-        const double fnew = -tt[0] + tt[1] + tt[2];
-        fdiff = std::fabs(fnew - fold);
-        fold = fnew;
-        if (std::isnan(fold) || std::isinf(fold)) { out->status = 2; break; }
-        if (fdiff < learning_conv_crit) { out->status = 1; break; }
-        std::vector<u32> na(d->na);  // learning_step (bp.cpp:53-75)
-        u32 rest = N;
-        const double snap = std::min(d->learn_snap * double(N) * double(learning_conv_crit), 0.01);
-        for (u32 i = 0; i + 1 < Q; ++i) {
-            na[i] = unsigned(int(learning_rate * na_e[i] + (1.0 - learning_rate) * na[i] + snap));
-            rest -= na[i];
+    struct front_end {
+        sbmbp_dist *d;
+        u32 max_sweeps;
+        double damping;
+        sbmbp_learn_result *out;
+        int converge(const double *crit, const uint8_t *, u32 *executed) {
+            const u64 sweeps0 = d->total_sweeps;
+            int niter;
+            double last;
+            CHK(run(d, crit[0], max_sweeps, damping, &niter, &last));
+            executed[0] = u32(d->total_sweeps - sweeps0);
+            return SBMBP_OK;
         }
-        na[Q - 1] = rest;
-        std::vector<double> cab(d->cab);
-        for (size_t a = 0; a < size_t(Q) * Q; ++a) cab[a] = learning_rate * cab_e[a] + (1.0 - learning_rate) * cab[a];
-        CHK(apply_params(d, cab.data(), na.data(), d->beta));
-        out->em_steps++;
-    }
-    out->free_energy = fold;
-    out->total_sweeps = d->total_sweeps - sweeps0;
-    return overlap_of(d, &out->overlap, nullptr);
+        int expect(const uint8_t *, double *na_e, double *nna_e, double *cab_e, double *f) {
+            CHK(em_expect(d, na_e, nna_e, cab_e));
+            double tt[6];
+            CHK(fe_terms(d, false, tt));
+            *f = -tt[0] + tt[1] + tt[2];
+            return SBMBP_OK;
+        }
+        void params(u32, std::vector<u32> &na, std::vector<double> &cab) { na = d->na; cab = d->cab; }
+        int apply(u32, const u32 *na, const double *cab) { return apply_params(d, cab, na, d->beta); }
+        int finish(u32) { return overlap_of(d, &out->overlap, nullptr); }
+    } fe{d, learning_max_time, double(dumping_rate), out};
+    // the two rules of the synchronous EM loop (sbmbp_set_learning_schedule; DESIGN.md section 2), as sbmbp_learning
+    return sbmbp::em_loop(fe, 1, d->Q, d->plan.n_global, learning_conv_crit, learning_max_time, double(learning_rate), d->learn_snap, d->field_mix,
+                   d->learn_field_mix, out);
 }
 
 int sbmbp_dist_get_stats(sbmbp_dist_t *d, sbmbp_stats *out) {

@@ -16,6 +16,7 @@
 
 #include "../../include/sbmbp.h"
 #include "host_graph.h"
+#include "host_loops.h"
 #include "kernels.h"
 #include "kernels_wide.h"
 #include "kernels_batch.h"
@@ -313,6 +314,57 @@ int setup_hub_frags(sbmbp_engine *e, const std::vector<uint32_t> &hub_row, const
     return SBMBP_OK;
 }
 
+// What every engine holds of its graph, however it was created: row offsets, neighbour table (and the reverse index when
+// with_rev), the segment and hub tables of `plan` (with the fragment tables of the hub rows when hub_frags), the label and
+// clamp vectors, zeroed partials (allocated by the caller), the dc 1 constant and the dc 2 source rows. e->N / E2 / Q / dc /
+// stream are set. The uploads are complete on return.
+int setup_graph_tables(sbmbp_engine *e, const segment_plan_t &plan, const uint64_t *row_ptr, const uint32_t *nbr, const uint32_t *rev,
+                       bool with_rev, bool hub_frags) {
+    std::vector<uint32_t> rp32(size_t(e->N) + 1);
+    for (size_t i = 0; i <= e->N; ++i) rp32[i] = uint32_t(row_ptr[i]);
+    e->h_row_ptr = rp32;
+    e->n_blk = uint32_t(plan.blk_row.size() - 1);
+    e->n_hub = uint32_t(plan.hub_row.size());
+    CHK(dev_alloc(e, &e->d_row_ptr, rp32.size()));
+    HIPCHK(hipMemcpyAsync(e->d_row_ptr, rp32.data(), rp32.size() * 4, hipMemcpyHostToDevice, e->stream));
+    CHK(dev_alloc(e, &e->d_nbr, e->E2));
+    if (with_rev) CHK(dev_alloc(e, &e->d_rev, e->E2));
+    if (e->E2) {
+        HIPCHK(hipMemcpyAsync(e->d_nbr, nbr, e->E2 * 4, hipMemcpyHostToDevice, e->stream));
+        if (with_rev) HIPCHK(hipMemcpyAsync(e->d_rev, rev, e->E2 * 4, hipMemcpyHostToDevice, e->stream));
+    } else {  // the sweeps' branch-free loads read nbr[0] / rev[0] even when there are no edges
+        HIPCHK(hipMemsetAsync(e->d_nbr, 0, 4, e->stream));
+        if (with_rev) HIPCHK(hipMemsetAsync(e->d_rev, 0, 4, e->stream));
+    }
+    CHK(dev_alloc(e, &e->d_blk_row, plan.blk_row.size()));
+    CHK(dev_alloc(e, &e->d_blk_e0, plan.blk_e0.size()));
+    CHK(dev_alloc(e, &e->d_hub_row, plan.hub_row.size()));
+    CHK(dev_alloc(e, &e->d_hub_blk, plan.hub_blk.size()));
+    HIPCHK(hipMemcpyAsync(e->d_blk_row, plan.blk_row.data(), plan.blk_row.size() * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->d_blk_e0, plan.blk_e0.data(), plan.blk_e0.size() * 4, hipMemcpyHostToDevice, e->stream));
+    if (e->n_hub) {
+        HIPCHK(hipMemcpyAsync(e->d_hub_row, plan.hub_row.data(), plan.hub_row.size() * 4, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->d_hub_blk, plan.hub_blk.data(), plan.hub_blk.size() * 4, hipMemcpyHostToDevice, e->stream));
+    }
+    if (e->n_hub && hub_frags) CHK(setup_hub_frags(e, plan.hub_row, rp32));
+    CHK(dev_alloc(e, &e->d_true, e->N));
+    CHK(dev_alloc(e, &e->d_clamp, e->N));
+    HIPCHK(hipMemsetAsync(e->d_true, 0, size_t(e->N) * 4, e->stream));
+    HIPCHK(hipMemsetAsync(e->d_clamp, 0xff, size_t(e->N) * 4, e->stream));
+    HIPCHK(hipMemsetAsync(e->d_partials, 0, e->partials_cap * 8, e->stream));
+    if (e->dc == 1) {  // sum over the directed edges of these rows of log(d_i d_l) = 2 sum_i d_i log d_i (constant of f_site / f_edge)
+        double s = 0.0;
+        for (uint32_t i = 0; i < e->N; ++i) { const double d = double(rp32[i + 1] - rp32[i]); if (d > 0) s += 2.0 * d * std::log(d); }
+        e->sum_log_didl = s;
+    }
+    if (e->dc == 2) {
+        CHK(dev_alloc(e, &e->d_src, e->E2));
+        hipLaunchKernelGGL(k_fill_src, dim3((e->N + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->N, e->d_src);
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));  // rp32 is a local
+    return SBMBP_OK;
+}
+
 // marginal-gather update of hub rows [h0, h0 + nh): two launches over their fragments
 int launch_hub_psi(sbmbp_engine *e, hipStream_t st, uint32_t h0, uint32_t nh, double *Mio, const double *psi_old, double *psi_new,
                    const int32_t *clamp, const shard_io &io, const double *Mcmp, int first) {
@@ -478,6 +530,31 @@ int read_conv_state(sbmbp_engine *e, conv_state *cs) {
     return SBMBP_OK;
 }
 
+// the convergence state without blocking the host: record copies it into page-locked slot 0/1 behind the work queued so
+// far, wait blocks until that point of the stream and returns it
+int record_conv_state(sbmbp_engine *e, int slot) {
+    if (!e->h_cs) {
+        HIPCHK(hipHostMalloc(&e->h_cs, 2 * sizeof(conv_state), hipHostMallocDefault));
+        for (auto &ev : e->ev_cs) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    HIPCHK(hipMemcpyAsync(static_cast<conv_state *>(e->h_cs) + slot, reinterpret_cast<const char *>(e->d_P) + offsetof(dev_params, maxdiff),
+                          sizeof(conv_state), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipEventRecord(e->ev_cs[slot], e->stream));
+    return SBMBP_OK;
+}
+// the host's answer to a pause (adaptive relaxation asked for damping in the middle of a marginal-gather run): the queued
+// sweeps behind it were skipped; the run goes on in the message-gather form
+int resume_run(sbmbp_engine *e) {
+    hipLaunchKernelGGL(k_resume, dim3(1), dim3(64), 0, e->stream, e->d_P);
+    HIPCHK(hipGetLastError());
+    return SBMBP_OK;
+}
+int wait_conv_state(sbmbp_engine *e, int slot, conv_state *cs) {
+    HIPCHK(hipEventSynchronize(e->ev_cs[slot]));
+    *cs = static_cast<conv_state *>(e->h_cs)[slot];
+    return SBMBP_OK;
+}
+
 // exact criterion of the reference's converge(): max |m^{t+1} - m^t| over the two message buffers
 int message_diff(sbmbp_engine *e, double *out) {
     const uint64_t n = e->E2;  // message records
@@ -628,11 +705,6 @@ int run_sweeps_coloured(sbmbp_engine *e, double crit, uint32_t max_sweeps, doubl
     CHK(upload_params(e, crit, false));
     CHK(launch_field(e, 1));
     CHK(ensure_partials(e, size_t(std::max<uint32_t>(std::max(e->n_blk, e->cs_max_rec), 1)) * (e->Q + 1)));
-    if (!e->h_cs) {
-        HIPCHK(hipHostMalloc(&e->h_cs, 2 * sizeof(conv_state), hipHostMallocDefault));
-        for (auto &ev : e->ev_cs) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    }
-    conv_state *slots = static_cast<conv_state *>(e->h_cs);
     conv_state cs{0.0, -1, 0, 0, 0, 0, 0, 1, 0, 0, -1};
     const uint32_t batch_max = std::max<uint32_t>(1, e->check_every);
     uint32_t done = 0;
@@ -640,29 +712,15 @@ int run_sweeps_coloured(sbmbp_engine *e, double crit, uint32_t max_sweeps, doubl
         const uint32_t batch = std::min(batch_max, max_sweeps - done);
         for (uint32_t b = 0; b < batch; ++b) CHK(launch_coloured_sweep(e, damping));
         done += batch;
-        HIPCHK(hipMemcpyAsync(&slots[slot], reinterpret_cast<const char *>(e->d_P) + offsetof(dev_params, maxdiff), sizeof(conv_state),
-                              hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipEventRecord(e->ev_cs[slot], e->stream));
+        return record_conv_state(e, slot);
+    };
+    auto wait_batch = [&](int slot, bool *stopped) -> int {
+        CHK(wait_conv_state(e, slot, &cs));
+        *stopped = cs.stop != 0;
         return SBMBP_OK;
     };
-    if (max_sweeps > 0) {
-        CHK(queue_batch(0));
-        for (int k = 0;; ++k) {
-            const bool more = done < max_sweeps;
-            if (more) CHK(queue_batch((k + 1) & 1));
-            HIPCHK(hipEventSynchronize(e->ev_cs[k & 1]));
-            cs = slots[k & 1];
-            if (cs.stop || !more) {
-                if (more) {  // drain the batch queued ahead (no-ops after a stop)
-                    HIPCHK(hipEventSynchronize(e->ev_cs[(k + 1) & 1]));
-                    cs = slots[(k + 1) & 1];
-                }
-                break;
-            }
-        }
-    } else {
-        HIPCHK(hipStreamSynchronize(e->stream));
-    }
+    if (max_sweeps > 0) CHK(queue_ahead(max_sweeps, done, queue_batch, wait_batch));
+    else HIPCHK(hipStreamSynchronize(e->stream));
     if (e->timing) CHK(collect_timing(e));
     const uint32_t executed = uint32_t(cs.sweep_idx);
     e->sweeps += executed;
@@ -693,80 +751,23 @@ int run_sweeps(sbmbp_engine *e, double crit, uint32_t max_sweeps, double damping
     CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (e->Q + 1)));
     CHK(upload_params(e, crit, psi_ok));
     CHK(launch_field(e, 1));
-    CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (e->Q + 1)));
-    uint32_t done = 0;
     conv_state cs{0.0, -1, 0, 0, 0, 0, 0, 1, 0, 0, -1};
-    const uint32_t batch_max = std::max<uint32_t>(1, e->check_every);
     // the first sweep after a state or parameter change gathers the messages themselves (explicit form), unless the
     // state is the device initialisation "message = sender's marginal", which the marginal-gather form starts from
     const bool first_from_psi = psi_ok && e->init_from_psi;
     const bool first_explicit = !e->psi_consistent && !first_from_psi;
-    // Batches are queued one ahead: while the host waits for the convergence state of batch k, batch k+1 is already in
-    // the stream, so the GPU never idles at a batch boundary.
-    if (!e->h_cs) {
-        HIPCHK(hipHostMalloc(&e->h_cs, 2 * sizeof(conv_state), hipHostMallocDefault));
-        for (auto &ev : e->ev_cs) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    }
-    conv_state *slots = static_cast<conv_state *>(e->h_cs);
-    // Batch sizes follow the decay of the reported difference: from two readings the host estimates the rate per sweep and
-    // how many sweeps are still needed, and queues no more than that (minus what is already in the stream), so that only a
-    // sweep or two are left as no-ops behind the stop.
-    uint32_t next_batch = batch_max;
-    double prev_md = -1.0;
-    int prev_idx = 0;
-    auto plan_next = [&](const conv_state &st) {
-        if (crit > 0 && prev_md > 0 && st.maxdiff > 0 && st.maxdiff < prev_md && st.sweep_idx > prev_idx) {
-            const double rate = std::pow(st.maxdiff / prev_md, 1.0 / double(st.sweep_idx - prev_idx));
-            const double need = st.maxdiff > crit ? std::ceil(std::log(crit / st.maxdiff) / std::log(rate)) : 1.0;
-            const double ahead = double(done) - double(st.sweep_idx);  // queued, not yet seen
-            next_batch = uint32_t(std::min<double>(batch_max, std::max(1.0, need - ahead)));
-        } else {
-            next_batch = batch_max;
-        }
-        if (st.maxdiff > 0) { prev_md = st.maxdiff; prev_idx = st.sweep_idx; }
-    };
-    bool form_psi = psi_ok;  // adaptive relaxation can ask for damping in the middle of a run: the rest runs in the message-gather form
+    batch_planner plan(std::max<uint32_t>(1, e->check_every), crit);
     uint32_t psi_count = 0;
-    auto queue_batch = [&](int slot) -> int {
-        const uint32_t batch = std::min(next_batch, max_sweeps - done);
-        for (uint32_t b = 0; b < batch; ++b) {
-            const uint32_t j = done + b;
+    // (adaptive relaxation can ask for damping in the middle of a run: converge_run queues the rest in the message-gather form)
+    auto queue_batch = [&](int slot, uint32_t first, uint32_t n, bool form_psi) -> int {
+        for (uint32_t j = first; j < first + n; ++j) {
             const bool pf = form_psi && !(j == 0 && first_explicit);
             CHK(launch_sweep(e, j, damping, pf, pf && j == 0 && first_from_psi));
         }
-        done += batch;
-        HIPCHK(hipMemcpyAsync(&slots[slot], reinterpret_cast<const char *>(e->d_P) + offsetof(dev_params, maxdiff), sizeof(conv_state),
-                              hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipEventRecord(e->ev_cs[slot], e->stream));
-        return SBMBP_OK;
+        return record_conv_state(e, slot);
     };
-    while (done < max_sweeps) {
-        const uint32_t start = done;
-        CHK(queue_batch(0));
-        for (int k = 0;; ++k) {
-            const bool more = done < max_sweeps;
-            if (more) CHK(queue_batch((k + 1) & 1));
-            HIPCHK(hipEventSynchronize(e->ev_cs[k & 1]));
-            cs = slots[k & 1];
-            plan_next(cs);
-            if (cs.stop || !more) {
-                if (more) {  // drain the batch queued ahead (no-ops after a stop)
-                    HIPCHK(hipEventSynchronize(e->ev_cs[(k + 1) & 1]));
-                    cs = slots[(k + 1) & 1];
-                }
-                break;
-            }
-        }
-        if (form_psi) psi_count += uint32_t(cs.sweep_idx) - start - ((first_explicit && start == 0 && cs.sweep_idx > 0) ? 1 : 0);
-        if (!(cs.stop && cs.pause)) break;
-        // the device asked for damped sweeps (dev_params::pause): what was queued behind that sweep did not run
-        done = uint32_t(cs.sweep_idx);
-        form_psi = false;
-        hipLaunchKernelGGL(k_resume, dim3(1), dim3(64), 0, e->stream, e->d_P);
-        HIPCHK(hipGetLastError());
-        next_batch = batch_max;
-        prev_md = -1.0;
-    }
+    auto wait_batch = [&](int slot, conv_state *st) { return wait_conv_state(e, slot, st); };
+    CHK(converge_run(max_sweeps, plan, psi_ok, first_explicit, queue_batch, wait_batch, [&]() { return resume_run(e); }, &cs, &psi_count));
     if (e->timing) CHK(collect_timing(e));
     const uint32_t executed = uint32_t(cs.sweep_idx);
     e->cur = (e->cur + int(executed)) & 1;
@@ -1224,24 +1225,6 @@ int overlap_impl(sbmbp_engine *e, double *ov, double *Cout) {
     return SBMBP_OK;
 }
 
-// learning_step (bp.cpp:53-75) on the host, for the single engine and the replica batch alike.
-// bp.cpp:58-63 truncates lr*na_expect + (1-lr)*na to an integer. na_expect is a sum of N marginals, each known to
-// the BP criterion, so a value within snap = min(learn_snap * N * crit, 0.01) below an integer is that integer as
-// far as the fixed point is known (README run: 500 - 9e-5 with the relaxed field, 500 - 1.6e-7 without, on a
-// symmetric instance whose exact value is 500; the reference's own schedule happens to land at 500 + 4e-8).
-// Values further below an integer truncate exactly as in the reference.
-void learning_step_host(uint32_t Q, uint32_t N, double learning_rate, double learn_snap, double crit, const double *na_e,
-                        const double *cab_e, uint32_t *na, double *cab) {
-    uint32_t rest = N;
-    const double snap = std::min(learn_snap * double(N) * crit, 0.01);
-    for (uint32_t i = 0; i + 1 < Q; ++i) {
-        na[i] = unsigned(int(learning_rate * na_e[i] + (1.0 - learning_rate) * na[i] + snap));
-        rest -= na[i];
-    }
-    na[Q - 1] = rest;
-    for (uint32_t a = 0; a < Q * Q; ++a) cab[a] = learning_rate * cab_e[a] + (1.0 - learning_rate) * cab[a];
-}
-
 // which of n runs is best (sbmbp.h: sbmbp_best_replica)
 uint32_t best_replica(uint32_t n, const double *f, const int *rank, int n_ranks) {
     int pick = -1;
@@ -1366,8 +1349,8 @@ int sbmbp_param_from_direct(uint32_t N, uint32_t Q, const double *pa, const doub
     return SBMBP_OK;
 }
 
-int sbmbp_create(sbmbp_engine_t **out, const sbmbp_graph_t *g, uint32_t Q, uint32_t dc, int device) {
-    if (!out || !g) return arg_error(__func__, __LINE__);
+// sbmbp_create; own_state = false leaves the message, marginal and parameter buffers to the caller (the replica batch)
+static int create_engine(sbmbp_engine_t **out, const sbmbp_graph_t *g, uint32_t Q, uint32_t dc, int device, bool own_state) {
     if (Q < 2 || Q > SBMBP_MAX_Q) { set_error("Q must be in [2, 64]"); return SBMBP_ERR_UNSUPPORTED; }
     if (dc > 2) { set_error("deg_corr_flag must be 0, 1 or 2"); return SBMBP_ERR_ARG; }
     if (Q > 16 && dc == 2) { set_error("deg_corr_flag 2 is implemented up to Q = 16"); return SBMBP_ERR_UNSUPPORTED; }
@@ -1388,98 +1371,44 @@ int sbmbp_create(sbmbp_engine_t **out, const sbmbp_graph_t *g, uint32_t Q, uint3
     e->E2 = g->e2();
     HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     e->own_stream = true;
-
-    // work decomposition: greedy segments of <= CAP edges and <= RCAP rows; a row above CAP is a hub segment
-    const uint32_t cap = uint32_t(frame_cap(Q)), rcap = uint32_t(frame_rcap(Q));
-    std::vector<uint32_t> blk_row, hub_row, hub_blk;
-    blk_row.push_back(0);
-    uint32_t rows = 0, edges = 0;
-    for (uint32_t i = 0; i < g->n; ++i) {
-        const uint32_t d = g->deg(i);
-        if (d > cap) {
-            if (rows) { blk_row.push_back(i); rows = 0; edges = 0; }
-            hub_row.push_back(i);
-            hub_blk.push_back(uint32_t(blk_row.size() - 1));
-            blk_row.push_back(i + 1);
-            continue;
+    const int r = [&]() -> int {
+        segment_plan_t plan;  // one chunk: the shard's decomposition (sbmbp_shard_create) without boundaries inside
+        segment_plan(g->row_ptr.data(), g->n, uint32_t(frame_cap(Q)), uint32_t(frame_rcap(Q)), {}, plan);
+        CHK(ensure_partials(e, (plan.blk_row.size() - 1) * (QMAX + 1)));
+        CHK(setup_graph_tables(e, plan, g->row_ptr.data(), g->nbr.data(), g->rev.data(), true, !e->wide));  // (the wide sweep walks a long row itself)
+        if (own_state) {
+            CHK(dev_alloc(e, &e->d_M[0], std::max<uint64_t>(e->E2, 1) * rec_len(e)));  // records of Q-1 components (Q above 16 labels); >= one record: the sweep's loads are branch-free
+            CHK(dev_alloc(e, &e->d_M[1], std::max<uint64_t>(e->E2, 1) * rec_len(e)));
+            CHK(dev_alloc(e, &e->d_psi[0], size_t(e->N) * Q));
+            CHK(dev_alloc(e, &e->d_psi[1], size_t(e->N) * Q));
+            CHK(dev_alloc(e, &e->d_P, 1));
         }
-        if (rows + 1 > rcap || edges + d > cap) { blk_row.push_back(i); rows = 0; edges = 0; }
-        rows++;
-        edges += d;
-    }
-    if (blk_row.back() != g->n) blk_row.push_back(g->n);
-    e->n_blk = uint32_t(blk_row.size() - 1);
-    e->n_hub = uint32_t(hub_row.size());
-
-    std::vector<uint32_t> rp32(size_t(g->n) + 1);
-    for (size_t i = 0; i <= g->n; ++i) rp32[i] = uint32_t(g->row_ptr[i]);
-    e->h_row_ptr = rp32;
-    int r;
-#define TRY(x) if ((r = (x)) != SBMBP_OK) { sbmbp_destroy(e); return r; }
-#define TRYHIP(x) do { hipError_t _h = (x); if (_h != hipSuccess) { set_error(std::string(#x) + ": " + hipGetErrorString(_h)); sbmbp_destroy(e); return SBMBP_ERR_HIP; } } while (0)
-    TRY(dev_alloc(e, &e->d_row_ptr, rp32.size()));
-    TRY(dev_alloc(e, &e->d_rev, e->E2));
-    TRY(dev_alloc(e, &e->d_nbr, e->E2));
-    TRY(dev_alloc(e, &e->d_blk_row, blk_row.size()));
-    TRY(dev_alloc(e, &e->d_blk_e0, blk_row.size()));
-    TRY(dev_alloc(e, &e->d_hub_row, hub_row.size()));
-    TRY(dev_alloc(e, &e->d_hub_blk, hub_blk.size()));
-    TRY(dev_alloc(e, &e->d_true, e->N));
-    TRY(dev_alloc(e, &e->d_clamp, e->N));
-    TRY(dev_alloc(e, &e->d_M[0], std::max<uint64_t>(e->E2, 1) * rec_len(e)));  // records of Q-1 components (Q above 16 labels); >= one record: the sweep's loads are branch-free
-    TRY(dev_alloc(e, &e->d_M[1], std::max<uint64_t>(e->E2, 1) * rec_len(e)));
-    if (e->wide) TRY(dev_alloc(e, &e->d_Pw, 1));
-    TRY(dev_alloc(e, &e->d_psi[0], size_t(e->N) * Q));
-    TRY(dev_alloc(e, &e->d_psi[1], size_t(e->N) * Q));
-    TRY(dev_alloc(e, &e->d_P, 1));
-    TRY(dev_alloc(e, &e->d_mats, 3 * Q * Q));
-    if (const char *fr = std::getenv("SBMBP_FUSED_REDUCTIONS")) e->fused_reductions = std::atoi(fr);
-    e->hist_cap = 4096;
-    TRY(dev_alloc(e, &e->d_hist, e->hist_cap));
-    TRY(ensure_partials(e, size_t(e->n_blk) * (QMAX + 1)));
-    TRY(dev_alloc(e, &e->d_fold_counters, 1));
-    TRYHIP(hipMemsetAsync(e->d_fold_counters, 0, 4, e->stream));
-    TRY(ensure_small(e, 8192));
-    TRY(dev_alloc(e, &e->d_stage, size_t(FOLD_BLOCKS) * FOLD_STRIDE_MAX));
-    TRYHIP(hipMemcpyAsync(e->d_row_ptr, rp32.data(), rp32.size() * 4, hipMemcpyHostToDevice, e->stream));
-    if (e->E2) {
-        TRYHIP(hipMemcpyAsync(e->d_rev, g->rev.data(), e->E2 * 4, hipMemcpyHostToDevice, e->stream));
-        TRYHIP(hipMemcpyAsync(e->d_nbr, g->nbr.data(), e->E2 * 4, hipMemcpyHostToDevice, e->stream));
-    } else {  // the sweeps' branch-free loads read nbr[0] / rev[0] even when there are no edges
-        TRYHIP(hipMemsetAsync(e->d_rev, 0, 4, e->stream));
-        TRYHIP(hipMemsetAsync(e->d_nbr, 0, 4, e->stream));
-    }
-    std::vector<uint32_t> blk_e0(blk_row.size());  // edge offset of every segment start, next to the row range
-    for (size_t b = 0; b < blk_row.size(); ++b) blk_e0[b] = rp32[blk_row[b]];
-    TRYHIP(hipMemcpyAsync(e->d_blk_row, blk_row.data(), blk_row.size() * 4, hipMemcpyHostToDevice, e->stream));
-    TRYHIP(hipMemcpyAsync(e->d_blk_e0, blk_e0.data(), blk_e0.size() * 4, hipMemcpyHostToDevice, e->stream));
-    if (e->n_hub) {
-        TRYHIP(hipMemcpyAsync(e->d_hub_row, hub_row.data(), hub_row.size() * 4, hipMemcpyHostToDevice, e->stream));
-        TRYHIP(hipMemcpyAsync(e->d_hub_blk, hub_blk.data(), hub_blk.size() * 4, hipMemcpyHostToDevice, e->stream));
-        if (!e->wide) TRY(setup_hub_frags(e, hub_row, rp32));  // (the wide sweep walks a long row itself)
-    }
-    TRYHIP(hipMemsetAsync(e->d_true, 0, size_t(e->N) * 4, e->stream));
-    TRYHIP(hipMemsetAsync(e->d_clamp, 0xff, size_t(e->N) * 4, e->stream));
-    TRYHIP(hipMemsetAsync(e->d_partials, 0, e->partials_cap * 8, e->stream));
-    if (dc == 2) {
-        TRY(dev_alloc(e, &e->d_src, e->E2));
-        hipLaunchKernelGGL(k_fill_src, dim3((e->N + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->N, e->d_src);
-        std::vector<uint32_t> deg(e->N);
-        for (uint32_t i = 0; i < g->n; ++i) deg[i] = g->deg(i);
-        TRY(dev_alloc(e, &e->d_deg, e->N));
-        TRYHIP(hipMemcpyAsync(e->d_deg, deg.data(), size_t(e->N) * 4, hipMemcpyHostToDevice, e->stream));
-        TRYHIP(hipStreamSynchronize(e->stream));  // deg is a local
-    }
-    if (dc == 1) {  // sum over directed edges of log(d_i d_l) = 2 sum_i d_i log d_i
-        double s = 0.0;
-        for (uint32_t i = 0; i < g->n; ++i) { const double d = double(g->deg(i)); if (d > 0) s += 2.0 * d * std::log(d); }
-        e->sum_log_didl = s;
-    }
-    TRYHIP(hipStreamSynchronize(e->stream));
-#undef TRY
-#undef TRYHIP
+        if (e->wide) CHK(dev_alloc(e, &e->d_Pw, 1));
+        CHK(dev_alloc(e, &e->d_mats, 3 * Q * Q));
+        if (const char *fr = std::getenv("SBMBP_FUSED_REDUCTIONS")) e->fused_reductions = std::atoi(fr);
+        e->hist_cap = 4096;
+        CHK(dev_alloc(e, &e->d_hist, e->hist_cap));
+        CHK(dev_alloc(e, &e->d_fold_counters, 1));
+        HIPCHK(hipMemsetAsync(e->d_fold_counters, 0, 4, e->stream));
+        CHK(ensure_small(e, 8192));
+        CHK(dev_alloc(e, &e->d_stage, size_t(FOLD_BLOCKS) * FOLD_STRIDE_MAX));
+        std::vector<uint32_t> deg(dc == 2 ? e->N : 0);
+        if (dc == 2) {
+            for (uint32_t i = 0; i < g->n; ++i) deg[i] = g->deg(i);
+            CHK(dev_alloc(e, &e->d_deg, e->N));
+            HIPCHK(hipMemcpyAsync(e->d_deg, deg.data(), size_t(e->N) * 4, hipMemcpyHostToDevice, e->stream));
+        }
+        HIPCHK(hipStreamSynchronize(e->stream));  // (deg is a local)
+        return SBMBP_OK;
+    }();
+    if (r != SBMBP_OK) { sbmbp_destroy(e); return r; }
     *out = e;
     return SBMBP_OK;
+}
+
+int sbmbp_create(sbmbp_engine_t **out, const sbmbp_graph_t *g, uint32_t Q, uint32_t dc, int device) {
+    if (!out || !g) return arg_error(__func__, __LINE__);
+    return create_engine(out, g, Q, dc, device, true);
 }
 
 void sbmbp_destroy(sbmbp_engine_t *e) {
@@ -1905,44 +1834,38 @@ int sbmbp_learning(sbmbp_engine_t *e, float learning_conv_crit, uint32_t learnin
     if (!e || !out) return arg_error(__func__, __LINE__);
     NOT_SHARD(e);
     if (!e->have_params || !e->have_state) { set_error("set_params and init_messages must precede learning"); return SBMBP_ERR_STATE; }
-    const uint32_t Q = e->Q;
-    std::vector<double> na_e(Q), nna_e(Q), cab_e(Q * Q);
-    double fold = 0.0, fdiff = 1.0;
     // The reference maintains the global field h incrementally inside its random-sequential sweeps; in the synchronous
     // schedule h lags one sweep, and with poorly matched parameters (the early EM steps) that lag keeps BP near a
     // symmetric saddle the reference leaves (fixture q4_learn_seed2). Relaxing the field, S <- (1-a) S + a sum psi, has
-    // the same fixed points and follows the reference there; a = 1 restores plain Jacobi.
-    const double keep_mix = e->field_mix;
-    e->field_mix = std::min(e->field_mix, e->learn_field_mix);
-    struct restore { sbmbp_engine *e; double v; ~restore() { e->field_mix = v; } } restore_mix{e, keep_mix};
-    out->em_steps = 0;
-    out->status = 0;
-    out->total_sweeps = 0;
-    const uint64_t sweeps0 = e->sweeps;
-    for (uint32_t t = 0; t < learning_max_time; ++t) {  // belief_propagation::learning (bp.cpp:27-47)
-        if (fdiff < learning_conv_crit) learning_conv_crit = float(double(learning_conv_crit) * 0.1);
-        int niter;
-        double last;
-        CHK(run_sweeps(e, double(learning_conv_crit), learning_max_time, double(dumping_rate), &niter, &last));
-        CHK(em_expect(e, na_e.data(), nna_e.data(), cab_e.data()));
-        double fnew;
-        CHK(free_energy_impl(e, &fnew, nullptr));
-        fdiff = std::fabs(fnew - fold);
-        fold = fnew;
-        if (std::isnan(fold) || std::isinf(fold)) { out->status = 2; break; }
-        if (fdiff < learning_conv_crit) { out->status = 1; break; }
-        std::vector<uint32_t> na(e->na);
-        std::vector<double> cab(e->cab);
-        learning_step_host(Q, e->N, double(learning_rate), e->learn_snap, double(learning_conv_crit), na_e.data(), cab_e.data(), na.data(), cab.data());
-        apply_params_host(e, cab.data(), na.data(), e->beta);
-        out->em_steps++;
-    }
-    out->free_energy = fold;
-    out->total_sweeps = e->sweeps - sweeps0;
-    CHK(upload_params(e, 0.0));
-    e->field_fresh = false;  // (the parameter block starts from a zero field again)
-    CHK(overlap_impl(e, &out->overlap, nullptr));
-    return SBMBP_OK;
+    // the same fixed points and follows the reference there; a = 1 restores plain Jacobi. em_loop
+    // lowers field_mix to learn_field_mix for its duration.
+    struct front_end {
+        sbmbp_engine *e;
+        uint32_t max_sweeps;  // of a BP run
+        double damping;
+        sbmbp_learn_result *out;
+        int converge(const double *crit, const uint8_t *, uint32_t *executed) {
+            const uint64_t sweeps0 = e->sweeps;
+            int niter;
+            double last;
+            CHK(run_sweeps(e, crit[0], max_sweeps, damping, &niter, &last));
+            executed[0] = uint32_t(e->sweeps - sweeps0);
+            return SBMBP_OK;
+        }
+        int expect(const uint8_t *, double *na_e, double *nna_e, double *cab_e, double *f) {
+            CHK(em_expect(e, na_e, nna_e, cab_e));
+            return free_energy_impl(e, f, nullptr);
+        }
+        void params(uint32_t, std::vector<uint32_t> &na, std::vector<double> &cab) { na = e->na; cab = e->cab; }
+        int apply(uint32_t, const uint32_t *na, const double *cab) { apply_params_host(e, cab, na, e->beta); return SBMBP_OK; }
+        int finish(uint32_t) {
+            CHK(upload_params(e, 0.0));
+            e->field_fresh = false;  // (the parameter block starts from a zero field again)
+            return overlap_impl(e, &out->overlap, nullptr);
+        }
+    } fe{e, learning_max_time, double(dumping_rate), out};
+    return em_loop(fe, 1, e->Q, e->N, learning_conv_crit, learning_max_time, double(learning_rate), e->learn_snap, e->field_mix,
+                   e->learn_field_mix, out);
 }
 
 int sbmbp_get_stats(sbmbp_engine_t *e, sbmbp_stats *out) {
@@ -2014,112 +1937,47 @@ int sbmbp_shard_create(sbmbp_engine_t **out, const sbmbp_shard_desc *d, uint32_t
     e->n_halo_msgs = d->n_halo_msgs;
     HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     e->own_stream = true;
-    const uint32_t cap = uint32_t(frame_cap(Q)), rcap = uint32_t(frame_rcap(Q));
-    std::vector<uint32_t> blk_row, hub_row, hub_blk, rp32(size_t(d->n_own) + 1);
     std::vector<uint32_t> chunk_row;  // segments never straddle a chunk boundary
     if (d->n_chunks > 1 && d->chunk_row) chunk_row.assign(d->chunk_row, d->chunk_row + d->n_chunks + 1);
     else chunk_row = {0u, d->n_own};
     if (chunk_row.front() != 0 || chunk_row.back() != d->n_own) { delete e; set_error("chunk_row must span [0, n_own]"); return SBMBP_ERR_ARG; }
     for (size_t c = 1; c < chunk_row.size(); ++c)
         if (chunk_row[c] < chunk_row[c - 1]) { delete e; set_error("chunk_row not monotone"); return SBMBP_ERR_ARG; }
-    blk_row.push_back(0);
-    uint32_t rows = 0, edges = 0;
-    size_t next_chunk = 1;
-    e->chunk_blk.push_back(0);
-    e->chunk_hub.push_back(0);
-    for (uint32_t i = 0; i < d->n_own; ++i) {
-        while (next_chunk < chunk_row.size() - 1 && i == chunk_row[next_chunk]) {  // close the open segment at a chunk boundary
-            if (rows) { blk_row.push_back(i); rows = 0; edges = 0; }
-            e->chunk_blk.push_back(uint32_t(blk_row.size() - 1));
-            e->chunk_hub.push_back(uint32_t(hub_row.size()));
-            ++next_chunk;
-        }
+    for (uint32_t i = 0; i < d->n_own; ++i)
         if (d->row_ptr[i + 1] < d->row_ptr[i]) {
             set_error("shard row_ptr not monotone at local row " + std::to_string(i) + " of " + std::to_string(d->n_own) + ": " +
                       std::to_string(d->row_ptr[i]) + " then " + std::to_string(d->row_ptr[i + 1]) + " (n_edges " + std::to_string(d->n_edges) + ")");
             delete e;
             return SBMBP_ERR_ARG;
         }
-        const uint32_t dg = uint32_t(d->row_ptr[i + 1] - d->row_ptr[i]);
-        if (dg > cap) {
-            if (rows) { blk_row.push_back(i); rows = 0; edges = 0; }
-            hub_row.push_back(i);
-            hub_blk.push_back(uint32_t(blk_row.size() - 1));
-            blk_row.push_back(i + 1);
-            continue;
+    const int r = [&]() -> int {
+        segment_plan_t plan;
+        segment_plan(d->row_ptr, d->n_own, uint32_t(frame_cap(Q)), uint32_t(frame_rcap(Q)), chunk_row, plan);
+        e->chunk_blk = plan.chunk_blk;
+        e->chunk_hub = plan.chunk_hub;
+        CHK(ensure_partials(e, std::max<size_t>(plan.blk_row.size() - 1, 64) * (QMAX + 1)));
+        CHK(setup_graph_tables(e, plan, d->row_ptr, d->nbr_local, d->rev_local, d->rev_local != nullptr, true));
+        // records of Q-1 components; >= one record: the sweep's loads are branch-free. With a reverse index the records received
+        // from the peers (the incoming messages of the cut edges) live behind the own ones, so rev addresses one array.
+        CHK(dev_alloc(e, &e->d_M[0], std::max<uint64_t>(e->E2 + e->n_halo_msgs, 1) * (Q - 1)));
+        CHK(dev_alloc(e, &e->d_M[1], std::max<uint64_t>(e->E2 + e->n_halo_msgs, 1) * (Q - 1)));
+        CHK(dev_alloc(e, &e->d_P, 1));
+        e->hist_cap = 4096;
+        CHK(dev_alloc(e, &e->d_hist, e->hist_cap));
+        if (dc == 2) {
+            CHK(dev_alloc(e, &e->d_deg, size_t(d->n_own) + d->n_halo));
+            HIPCHK(hipMemcpyAsync(e->d_deg, d->table_deg, (size_t(d->n_own) + d->n_halo) * 4, hipMemcpyHostToDevice, e->stream));
         }
-        if (rows + 1 > rcap || edges + dg > cap) { blk_row.push_back(i); rows = 0; edges = 0; }
-        rows++;
-        edges += dg;
-    }
-    if (blk_row.back() != d->n_own) blk_row.push_back(d->n_own);
-    while (e->chunk_blk.size() < chunk_row.size()) {  // trailing (possibly empty) chunks and the end sentinel
-        e->chunk_blk.push_back(uint32_t(blk_row.size() - 1));
-        e->chunk_hub.push_back(uint32_t(hub_row.size()));
-    }
-    for (size_t i = 0; i <= d->n_own; ++i) rp32[i] = uint32_t(d->row_ptr[i]);
-    e->h_row_ptr = rp32;
-    e->n_blk = uint32_t(blk_row.size() - 1);
-    e->n_hub = uint32_t(hub_row.size());
-    int r;
-#define TRY(x) if ((r = (x)) != SBMBP_OK) { sbmbp_destroy(e); return r; }
-#define TRYHIP(x) do { hipError_t _h = (x); if (_h != hipSuccess) { set_error(std::string(#x) + ": " + hipGetErrorString(_h)); sbmbp_destroy(e); return SBMBP_ERR_HIP; } } while (0)
-    TRY(dev_alloc(e, &e->d_row_ptr, rp32.size()));
-    TRY(dev_alloc(e, &e->d_nbr, e->E2));
-    TRY(dev_alloc(e, &e->d_blk_row, blk_row.size()));
-    TRY(dev_alloc(e, &e->d_blk_e0, blk_row.size()));
-    TRY(dev_alloc(e, &e->d_hub_row, hub_row.size()));
-    TRY(dev_alloc(e, &e->d_hub_blk, hub_blk.size()));
-    TRY(dev_alloc(e, &e->d_true, e->N));
-    TRY(dev_alloc(e, &e->d_clamp, e->N));
-    // records of Q-1 components; >= one record: the sweep's loads are branch-free. With a reverse index the records received
-    // from the peers (the incoming messages of the cut edges) live behind the own ones, so rev addresses one array.
-    TRY(dev_alloc(e, &e->d_M[0], std::max<uint64_t>(e->E2 + e->n_halo_msgs, 1) * (Q - 1)));
-    TRY(dev_alloc(e, &e->d_M[1], std::max<uint64_t>(e->E2 + e->n_halo_msgs, 1) * (Q - 1)));
-    TRY(dev_alloc(e, &e->d_P, 1));
-    e->hist_cap = 4096;
-    TRY(dev_alloc(e, &e->d_hist, e->hist_cap));
-    if (d->rev_local) {
-        TRY(dev_alloc(e, &e->d_rev, e->E2));
-        if (e->E2) TRYHIP(hipMemcpyAsync(e->d_rev, d->rev_local, e->E2 * 4, hipMemcpyHostToDevice, e->stream));
-        else TRYHIP(hipMemsetAsync(e->d_rev, 0, 4, e->stream));
-    }
-    if (dc == 2) {
-        TRY(dev_alloc(e, &e->d_deg, size_t(d->n_own) + d->n_halo));
-        TRYHIP(hipMemcpyAsync(e->d_deg, d->table_deg, (size_t(d->n_own) + d->n_halo) * 4, hipMemcpyHostToDevice, e->stream));
-        TRY(dev_alloc(e, &e->d_src, e->E2));
-    }
-    TRYHIP(hipMemsetAsync(e->d_clamp, 0xff, size_t(e->N) * 4, e->stream));
-    if (e->n_halo_msgs) {  // defined content before the first exchange
-        TRYHIP(hipMemsetAsync(e->d_M[0] + e->E2 * (Q - 1), 0, e->n_halo_msgs * (Q - 1) * 8, e->stream));
-        TRYHIP(hipMemsetAsync(e->d_M[1] + e->E2 * (Q - 1), 0, e->n_halo_msgs * (Q - 1) * 8, e->stream));
-    }
-    TRY(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 64)) * (QMAX + 1)));
-    TRY(ensure_small(e, 8192));
-    TRY(dev_alloc(e, &e->d_stage, size_t(FOLD_BLOCKS) * FOLD_STRIDE_MAX));
-    TRYHIP(hipMemcpyAsync(e->d_row_ptr, rp32.data(), rp32.size() * 4, hipMemcpyHostToDevice, e->stream));
-    if (e->E2) TRYHIP(hipMemcpyAsync(e->d_nbr, d->nbr_local, e->E2 * 4, hipMemcpyHostToDevice, e->stream));
-    else TRYHIP(hipMemsetAsync(e->d_nbr, 0, 4, e->stream));  // the sweep's branch-free loads read nbr[0] even without edges
-    std::vector<uint32_t> blk_e0(blk_row.size());  // edge offset of every segment start, next to the row range
-    for (size_t b = 0; b < blk_row.size(); ++b) blk_e0[b] = rp32[blk_row[b]];
-    TRYHIP(hipMemcpyAsync(e->d_blk_row, blk_row.data(), blk_row.size() * 4, hipMemcpyHostToDevice, e->stream));
-    TRYHIP(hipMemcpyAsync(e->d_blk_e0, blk_e0.data(), blk_e0.size() * 4, hipMemcpyHostToDevice, e->stream));
-    if (e->n_hub) {
-        TRYHIP(hipMemcpyAsync(e->d_hub_row, hub_row.data(), hub_row.size() * 4, hipMemcpyHostToDevice, e->stream));
-        TRYHIP(hipMemcpyAsync(e->d_hub_blk, hub_blk.data(), hub_blk.size() * 4, hipMemcpyHostToDevice, e->stream));
-        TRY(setup_hub_frags(e, hub_row, rp32));
-    }
-    TRYHIP(hipMemsetAsync(e->d_true, 0, size_t(e->N) * 4, e->stream));
-    TRYHIP(hipMemsetAsync(e->d_partials, 0, e->partials_cap * 8, e->stream));
-    if (dc == 2) hipLaunchKernelGGL(k_fill_src, dim3((e->N + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->N, e->d_src);
-    if (dc == 1) {  // sum over the owned rows of 2 d log d (their share of the dc 1 constant of f_site / f_edge)
-        double sdl = 0.0;
-        for (uint32_t i = 0; i < d->n_own; ++i) { const double dg = double(rp32[i + 1] - rp32[i]); if (dg > 0) sdl += 2.0 * dg * std::log(dg); }
-        e->sum_log_didl = sdl;
-    }
-    TRYHIP(hipStreamSynchronize(e->stream));
-#undef TRY
-#undef TRYHIP
+        if (e->n_halo_msgs) {  // defined content before the first exchange
+            HIPCHK(hipMemsetAsync(e->d_M[0] + e->E2 * (Q - 1), 0, e->n_halo_msgs * (Q - 1) * 8, e->stream));
+            HIPCHK(hipMemsetAsync(e->d_M[1] + e->E2 * (Q - 1), 0, e->n_halo_msgs * (Q - 1) * 8, e->stream));
+        }
+        CHK(ensure_small(e, 8192));
+        CHK(dev_alloc(e, &e->d_stage, size_t(FOLD_BLOCKS) * FOLD_STRIDE_MAX));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        return SBMBP_OK;
+    }();
+    if (r != SBMBP_OK) { sbmbp_destroy(e); return r; }
     *out = e;
     return SBMBP_OK;
 }
@@ -2212,28 +2070,18 @@ int sbmbp_shard_sweep_explicit(sbmbp_engine_t *e, uint32_t j, double damping) {
     return SBMBP_OK;
 }
 
-// the convergence state without blocking the host: record copies it into page-locked slot 0/1 behind the work queued so
-// far, wait blocks until that point of the stream and returns it
 int sbmbp_shard_state_record(sbmbp_engine_t *e, int slot) {
     device_scope dev_(e);
     IS_SHARD(e);
     if (slot < 0 || slot > 1) return arg_error(__func__, __LINE__);
-    if (!e->h_cs) {
-        HIPCHK(hipHostMalloc(&e->h_cs, 2 * sizeof(conv_state), hipHostMallocDefault));
-        for (auto &ev : e->ev_cs) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    }
-    conv_state *slots = static_cast<conv_state *>(e->h_cs);
-    HIPCHK(hipMemcpyAsync(&slots[slot], reinterpret_cast<const char *>(e->d_P) + offsetof(dev_params, maxdiff), sizeof(conv_state),
-                          hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipEventRecord(e->ev_cs[slot], e->stream));
-    return SBMBP_OK;
+    return record_conv_state(e, slot);
 }
 int sbmbp_shard_state_wait(sbmbp_engine_t *e, int slot, sbmbp_conv_state *out) {
     device_scope dev_(e);
     IS_SHARD(e);
     if (slot < 0 || slot > 1 || !out || !e->h_cs) return arg_error(__func__, __LINE__);
-    HIPCHK(hipEventSynchronize(e->ev_cs[slot]));
-    const conv_state &cs = static_cast<conv_state *>(e->h_cs)[slot];
+    conv_state cs;
+    CHK(wait_conv_state(e, slot, &cs));
     out->maxdiff = cs.maxdiff;
     out->conv_iter = cs.conv_iter;
     out->sweep_idx = cs.sweep_idx;
@@ -2245,14 +2093,10 @@ int sbmbp_shard_state_wait(sbmbp_engine_t *e, int slot, sbmbp_conv_state *out) {
     return SBMBP_OK;
 }
 
-// the host's answer to a pause (adaptive relaxation asked for damping in the middle of a marginal-gather run): the queued
-// sweeps behind it were skipped; the run goes on in the message-gather form
 int sbmbp_shard_resume(sbmbp_engine_t *e) {
     device_scope dev_(e);
     IS_SHARD(e);
-    hipLaunchKernelGGL(k_resume, dim3(1), dim3(64), 0, e->stream, e->d_P);
-    HIPCHK(hipGetLastError());
-    return SBMBP_OK;
+    return resume_run(e);
 }
 
 int sbmbp_shard_begin(sbmbp_engine_t *e, double crit, int hinted) {
@@ -2805,11 +2649,6 @@ int batch_launch_sweep(sbmbp_batch *b, const batch_view &bv, uint32_t j, double 
     return SBMBP_OK;
 }
 
-// run_sweeps for the batch: every replica starts from its current state, stops at its own sweep (device side, P[r].stop)
-// and keeps the state of that sweep; the call ends when all have stopped or after max_sweeps
-// crit[r] is replica r's criterion. active (null = all): a replica that is not active is frozen: its parameter block is not
-// uploaded again, its stop flag is set, and its state and parity stay untouched; executed[r] (may be null) = sweeps replica
-// r executed in this call.
 int batch_check_ready(const sbmbp_batch *b, const char *what) {
     for (uint32_t r = 0; r < b->R; ++r)
         if (!b->rep[r].have_params || !b->rep[r].have_state) {
@@ -2818,6 +2657,11 @@ int batch_check_ready(const sbmbp_batch *b, const char *what) {
         }
     return SBMBP_OK;
 }
+// run_sweeps for the batch: every replica starts from its current state, stops at its own sweep (device side, P[r].stop)
+// and keeps the state of that sweep; the call ends when all have stopped or after max_sweeps
+// crit[r] is replica r's criterion. active (null = all): a replica that is not active is frozen: its parameter block is not
+// uploaded again, its stop flag is set, and its state and parity stay untouched; executed[r] (may be null) = sweeps replica
+// r executed in this call.
 int batch_run(sbmbp_batch *b, const double *crit, const uint8_t *active, uint32_t max_sweeps, double damping, int *niter, double *last,
               uint32_t *executed_out = nullptr) {
     sbmbp_engine *e = b->e;
@@ -2856,27 +2700,13 @@ int batch_run(sbmbp_batch *b, const double *crit, const uint8_t *active, uint32_
         HIPCHK(hipEventRecord(b->ev_cs[slot], e->stream));
         return SBMBP_OK;
     };
-    auto all_stopped = [&](const conv_state *s) {
-        for (uint32_t r = 0; r < R; ++r) if (!s[r].stop) return false;
-        return true;
+    auto wait_batch = [&](int slot, bool *stopped) -> int {  // stopped = every replica has
+        HIPCHK(hipEventSynchronize(b->ev_cs[slot]));
+        std::copy(slots + size_t(slot) * R, slots + size_t(slot + 1) * R, cs.begin());
+        *stopped = std::all_of(cs.begin(), cs.end(), [](const conv_state &s) { return s.stop != 0; });
+        return SBMBP_OK;
     };
-    if (max_sweeps > 0) {
-        CHK(queue_batch(0));
-        for (int k = 0;; ++k) {
-            const bool more = done < max_sweeps;
-            if (more) CHK(queue_batch((k + 1) & 1));
-            HIPCHK(hipEventSynchronize(b->ev_cs[k & 1]));
-            const conv_state *s = slots + size_t(k & 1) * R;
-            if (all_stopped(s) || !more) {
-                if (more) {  // drain the batch queued ahead (no-ops: every replica has stopped)
-                    HIPCHK(hipEventSynchronize(b->ev_cs[(k + 1) & 1]));
-                    s = slots + size_t((k + 1) & 1) * R;
-                }
-                std::copy(s, s + R, cs.begin());
-                break;
-            }
-        }
-    }
+    CHK(queue_ahead(max_sweeps, done, queue_batch, wait_batch));
     for (uint32_t r = 0; r < R; ++r) {
         if (executed_out) executed_out[r] = 0;
         if (active && !active[r]) continue;  // frozen: P[r] still holds the records of its last run
@@ -3108,17 +2938,11 @@ int sbmbp_batch_create(sbmbp_batch_t **out, const sbmbp_graph_t *g, uint32_t Q, 
     if (dc > 2) { set_error("deg_corr_flag must be 0, 1 or 2"); return SBMBP_ERR_ARG; }
     if (Q > 16) { set_error("replica batches are implemented up to Q = 16 (the lane-per-edge kernels); Q = " + std::to_string(Q)); return SBMBP_ERR_UNSUPPORTED; }
     sbmbp_engine *e = nullptr;
-    CHK(sbmbp_create(&e, g, Q, dc, device));
+    CHK(create_engine(&e, g, Q, dc, device, false));  // the message, marginal and parameter buffers are the batch's
     device_scope dev_(e);
     auto *b = new sbmbp_batch();
     b->e = e;
     b->R = n_replicas;
-    // the engine's own state buffers give way to the batch's
-    void *own[] = {e->d_M[0], e->d_M[1], e->d_psi[0], e->d_psi[1], e->d_P};
-    for (void *p : own) if (p) (void)hipFree(p);
-    e->device_bytes -= (2 * std::max<uint64_t>(e->E2, 1) * (Q - 1) + 2 * uint64_t(e->N) * Q) * 8 + sizeof(dev_params);
-    e->d_M[0] = e->d_M[1] = e->d_psi[0] = e->d_psi[1] = nullptr;
-    e->d_P = nullptr;
     e->gather_mode = 1;  // message-gather form only: the reductions of a bound replica take the message-gather kernels too
     b->msg_stride = size_t(std::max<uint64_t>(e->E2, 1)) * (Q - 1);  // >= one record: the sweep's loads are branch-free
     b->psi_stride = size_t(e->N) * Q;
@@ -3340,50 +3164,36 @@ int sbmbp_batch_learning(sbmbp_batch_t *b, float learning_conv_crit, uint32_t le
     sbmbp_engine *e = b->e;
     device_scope dev_(e);
     const uint32_t R = b->R, Q = e->Q;
-    // the relaxed field of the EM loop's BP runs (sbmbp_learning)
-    const double keep_mix = e->field_mix;
-    e->field_mix = std::min(e->field_mix, e->learn_field_mix);
-    struct restore { sbmbp_engine *e; double v; ~restore() { e->field_mix = v; } } restore_mix{e, keep_mix};
-    std::vector<float> crit(R, learning_conv_crit);
-    std::vector<double> critd(R), fold(R, 0.0), fdiff(R, 1.0), fnew(R), na_e(size_t(R) * Q), nna_e(size_t(R) * Q), cab_e(size_t(R) * Q * Q);
-    std::vector<uint8_t> active(R, 1);
-    std::vector<uint32_t> executed(R);
-    for (uint32_t r = 0; r < R; ++r) { out[r].em_steps = 0; out[r].status = 0; out[r].total_sweeps = 0; }
-    uint32_t n_active = R;
-    for (uint32_t t = 0; t < learning_max_time && n_active; ++t) {  // belief_propagation::learning (bp.cpp:27-47), all replicas in step
-        for (uint32_t r = 0; r < R; ++r) {
-            if (active[r] && fdiff[r] < crit[r]) crit[r] = float(double(crit[r]) * 0.1);
-            critd[r] = double(crit[r]);
+    struct front_end {
+        sbmbp_batch *b;
+        uint32_t max_sweeps;
+        double damping;
+        sbmbp_learn_result *out;
+        int converge(const double *crit, const uint8_t *active, uint32_t *executed) {
+            return batch_run(b, crit, active, max_sweeps, damping, nullptr, nullptr, executed);
         }
-        CHK(batch_run(b, critd.data(), active.data(), learning_max_time, double(dumping_rate), nullptr, nullptr, executed.data()));
-        CHK(batch_reductions(b, active.data(), na_e.data(), nna_e.data(), cab_e.data(), fnew.data(), nullptr));
-        for (uint32_t r = 0; r < R; ++r) {
-            if (!active[r]) continue;
-            out[r].total_sweeps += executed[r];
-            fdiff[r] = std::fabs(fnew[r] - fold[r]);
-            fold[r] = fnew[r];
-            if (std::isnan(fold[r]) || std::isinf(fold[r])) out[r].status = 2;
-            else if (fdiff[r] < crit[r]) out[r].status = 1;
-            if (out[r].status) { active[r] = 0; --n_active; continue; }  // keeps the state and parameters of this round
-            std::vector<uint32_t> na(b->rep[r].na);
-            std::vector<double> cb(b->rep[r].cab);
-            learning_step_host(Q, e->N, double(learning_rate), e->learn_snap, double(crit[r]), na_e.data() + size_t(r) * Q,
-                               cab_e.data() + size_t(r) * Q * Q, na.data(), cb.data());
+        int expect(const uint8_t *active, double *na_e, double *nna_e, double *cab_e, double *f) {
+            return batch_reductions(b, active, na_e, nna_e, cab_e, f, nullptr);
+        }
+        void params(uint32_t r, std::vector<uint32_t> &na, std::vector<double> &cab) { na = b->rep[r].na; cab = b->rep[r].cab; }
+        int apply(uint32_t r, const uint32_t *na, const double *cab) {
             bound_replica v(b, r);
-            apply_params_host(e, cb.data(), na.data(), e->beta);
-            out[r].em_steps++;
+            apply_params_host(b->e, cab, na, b->e->beta);
+            return SBMBP_OK;
         }
-    }
+        int finish(uint32_t r) {
+            bound_replica v(b, r);
+            CHK(upload_params(b->e, 0.0));
+            b->e->field_fresh = false;  // (the parameter block starts from a zero field again)
+            return overlap_impl(b->e, &out[r].overlap, nullptr);
+        }
+    } fe{b, learning_max_time, double(dumping_rate), out};
+    CHK(em_loop(fe, R, Q, e->N, learning_conv_crit, learning_max_time, double(learning_rate), e->learn_snap, e->field_mix, e->learn_field_mix, out));
     std::vector<int> rank(R);
+    std::vector<double> fold(R);
     for (uint32_t r = 0; r < R; ++r) {
-        out[r].free_energy = fold[r];
+        fold[r] = out[r].free_energy;
         rank[r] = out[r].status == 1 ? 0 : (out[r].status == 0 ? 1 : -1);
-        {
-            bound_replica v(b, r);
-            CHK(upload_params(e, 0.0));
-            e->field_fresh = false;  // (the parameter block starts from a zero field again)
-            CHK(overlap_impl(e, &out[r].overlap, nullptr));
-        }
         const batch_replica &p = b->rep[r];
         if (eta) std::copy(p.eta.begin(), p.eta.end(), eta + size_t(r) * Q);
         if (cab) std::copy(p.cab.begin(), p.cab.end(), cab + size_t(r) * Q * Q);

@@ -598,4 +598,59 @@ int coloured_plan(uint32_t n, const uint64_t *row_ptr, const uint32_t *nbr, cons
     return SBMBP_OK;
 }
 
+void segment_plan(const uint64_t *row_ptr, uint32_t n, uint32_t cap, uint32_t rcap, const std::vector<uint32_t> &chunk_row,
+                  segment_plan_t &out) {
+    std::vector<uint32_t> &blk_row = out.blk_row;
+    const size_t n_chunks = chunk_row.empty() ? 1 : chunk_row.size() - 1;
+    out = segment_plan_t();
+    blk_row.push_back(0);
+    out.chunk_blk.push_back(0);
+    out.chunk_hub.push_back(0);
+    uint32_t rows = 0, edges = 0;
+    size_t next_chunk = 1;
+    for (uint32_t i = 0; i < n; ++i) {
+        while (next_chunk < n_chunks && i == chunk_row[next_chunk]) {  // close the open segment at a chunk boundary
+            if (rows) { blk_row.push_back(i); rows = 0; edges = 0; }
+            out.chunk_blk.push_back(uint32_t(blk_row.size() - 1));
+            out.chunk_hub.push_back(uint32_t(out.hub_row.size()));
+            ++next_chunk;
+        }
+        const uint64_t d = row_ptr[i + 1] - row_ptr[i];
+        if (d > cap) {
+            if (rows) { blk_row.push_back(i); rows = 0; edges = 0; }
+            out.hub_row.push_back(i);
+            out.hub_blk.push_back(uint32_t(blk_row.size() - 1));
+            blk_row.push_back(i + 1);
+            continue;
+        }
+        if (rows + 1 > rcap || edges + uint32_t(d) > cap) { blk_row.push_back(i); rows = 0; edges = 0; }
+        rows++;
+        edges += uint32_t(d);
+    }
+    if (blk_row.back() != n) blk_row.push_back(n);
+    while (out.chunk_blk.size() < n_chunks + 1) {  // trailing (possibly empty) chunks and the end sentinel
+        out.chunk_blk.push_back(uint32_t(blk_row.size() - 1));
+        out.chunk_hub.push_back(uint32_t(out.hub_row.size()));
+    }
+    out.blk_e0.resize(blk_row.size());  // edge offset of every segment start, next to the row range
+    for (size_t b = 0; b < blk_row.size(); ++b) out.blk_e0[b] = uint32_t(row_ptr[blk_row[b]]);
+}
+
+// bp.cpp:58-63 truncates lr*na_expect + (1-lr)*na to an integer. na_expect is a sum of N marginals, each known to
+// the BP criterion, so a value within snap = min(learn_snap * N * crit, 0.01) below an integer is that integer as
+// far as the fixed point is known (README run: 500 - 9e-5 with the relaxed field, 500 - 1.6e-7 without, on a
+// symmetric instance whose exact value is 500; the reference's own schedule happens to land at 500 + 4e-8).
+// Values further below an integer truncate exactly as in the reference.
+void learning_step_host(uint32_t Q, uint32_t N, double learning_rate, double learn_snap, double crit, const double *na_e,
+                        const double *cab_e, uint32_t *na, double *cab) {
+    uint32_t rest = N;
+    const double snap = std::min(learn_snap * double(N) * crit, 0.01);
+    for (uint32_t i = 0; i + 1 < Q; ++i) {
+        na[i] = unsigned(int(learning_rate * na_e[i] + (1.0 - learning_rate) * na[i] + snap));
+        rest -= na[i];
+    }
+    na[Q - 1] = rest;
+    for (uint32_t a = 0; a < Q * Q; ++a) cab[a] = learning_rate * cab_e[a] + (1.0 - learning_rate) * cab[a];
+}
+
 }  // namespace sbmbp

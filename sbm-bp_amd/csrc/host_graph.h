@@ -51,5 +51,19 @@ void init_state_host(uint32_t n, const uint32_t *row_ptr, uint64_t e2, uint32_t 
 int coloured_plan(uint32_t n, const uint64_t *row_ptr, const uint32_t *nbr, const uint32_t *colour_in, double step_fraction,
                   std::vector<uint32_t> &colour, std::vector<uint32_t> &step, uint32_t *n_colours, uint32_t *n_steps);
 
+// The work decomposition of a row range: greedy segments of at most cap edges and rcap rows; a row above cap is a hub
+// segment of its own. chunk_row = the row chunks' boundaries (first 0, last n, monotone; empty = one chunk [0, n]): no
+// segment straddles one. Segment b covers rows blk_row[b] .. blk_row[b + 1] and starts at edge blk_e0[b]; hub h is row
+// hub_row[h] = segment hub_blk[h]; chunk c owns segments chunk_blk[c] .. chunk_blk[c + 1] and hubs chunk_hub[c] .. [c + 1].
+struct segment_plan_t {
+    std::vector<uint32_t> blk_row, blk_e0, hub_row, hub_blk, chunk_blk, chunk_hub;
+};
+void segment_plan(const uint64_t *row_ptr, uint32_t n, uint32_t cap, uint32_t rcap, const std::vector<uint32_t> &chunk_row,
+                  segment_plan_t &out);
+
+// learning_step (bp.cpp:53-75): the new group sizes and affinities of one EM step, in place in na / cab
+void learning_step_host(uint32_t Q, uint32_t N, double learning_rate, double learn_snap, double crit, const double *na_e,
+                        const double *cab_e, uint32_t *na, double *cab);
+
 }  // namespace sbmbp
 #endif

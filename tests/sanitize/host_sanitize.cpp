@@ -2,6 +2,10 @@
 // builder, the std::mt19937-compatible initial state, parameter constructors) and the CPU restatement (oracle/bp_oracle.cpp)
 // built with -fsanitize=address,undefined and driven through their edge cases. CPU build only; no GPU code is involved.
 // Exit code 0 and no sanitizer report = pass (tests/test_capi_cpu.py::test_host_code_under_asan_ubsan).
+// Also the host drivers every front end shares: the segment plan (host_graph.h) against hand-worked tables and its
+// invariants, the batch planner against hand-worked values, and the queue-ahead loop, the convergence run and the EM loop
+// (host_loops.h) over scripted fakes, call for call against traces recorded from the loops they replaced (loop_fakes.h).
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +16,8 @@
 #include <vector>
 
 #include "../../sbm-bp_amd/csrc/host_graph.h"
+#include "../../sbm-bp_amd/csrc/host_loops.h"
+#include "loop_fakes.h"
 
 extern "C" {
 void *orc_graph_from_edges(const uint32_t *pairs, uint64_t n_pairs, uint32_t N);
@@ -163,9 +169,247 @@ static int run(const char *dataset) {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------ segment plan
+typedef std::vector<uint32_t> u32s;
+
+static int check_plan(const std::vector<uint64_t> &rp, uint32_t n, uint32_t cap, uint32_t rcap, const u32s &chunks, sbmbp::segment_plan_t &p) {
+    sbmbp::segment_plan(rp.data(), n, cap, rcap, chunks, p);
+    const u32s ch = chunks.empty() ? u32s{0u, n} : chunks;
+    const size_t nb = p.blk_row.size() - 1;
+    REQUIRE(p.blk_row.size() >= 1 && p.blk_row.front() == 0 && p.blk_row.back() == n && p.blk_e0.size() == p.blk_row.size());
+    REQUIRE(p.hub_row.size() == p.hub_blk.size());
+    REQUIRE(p.chunk_blk.size() == ch.size() && p.chunk_hub.size() == ch.size());
+    REQUIRE(p.chunk_blk.front() == 0 && p.chunk_blk.back() == nb && p.chunk_hub.front() == 0 && p.chunk_hub.back() == p.hub_row.size());
+    std::vector<char> is_hub(nb + 1, 0);
+    for (size_t h = 0; h < p.hub_row.size(); ++h) {
+        REQUIRE(p.hub_blk[h] < nb && p.blk_row[p.hub_blk[h]] == p.hub_row[h] && p.blk_row[p.hub_blk[h] + 1] == p.hub_row[h] + 1);
+        REQUIRE(rp[p.hub_row[h] + 1] - rp[p.hub_row[h]] > cap);
+        REQUIRE(h == 0 || p.hub_row[h] > p.hub_row[h - 1]);
+        is_hub[p.hub_blk[h]] = 1;
+    }
+    auto starts_chunk = [&](uint32_t row) { return std::find(ch.begin() + 1, ch.end() - 1, row) != ch.end() - 1; };
+    for (size_t b = 0; b < nb; ++b) {
+        const uint32_t r0 = p.blk_row[b], r1 = p.blk_row[b + 1];
+        REQUIRE(r0 < r1);  // strictly rising
+        REQUIRE(p.blk_e0[b] == rp[r0]);
+        for (size_t c = 1; c + 1 < ch.size(); ++c) REQUIRE(!(r0 < ch[c] && ch[c] < r1));  // no segment straddles a chunk boundary
+        if (is_hub[b]) continue;
+        const uint64_t edges = rp[r1] - rp[r0];
+        REQUIRE(edges <= cap && r1 - r0 <= rcap);
+        for (uint32_t i = r0; i < r1; ++i) REQUIRE(rp[i + 1] - rp[i] <= cap);
+        if (r1 < n) {  // closed for a reason: the next row would not fit, is a hub, or starts a chunk
+            const uint64_t d = rp[r1 + 1] - rp[r1];
+            REQUIRE(d > cap || edges + d > cap || r1 - r0 + 1 > rcap || starts_chunk(r1));
+        }
+    }
+    REQUIRE(p.blk_e0[nb] == rp[n]);
+    for (size_t c = 0; c + 1 < ch.size(); ++c) {
+        REQUIRE(p.chunk_blk[c] <= p.chunk_blk[c + 1] && p.chunk_hub[c] <= p.chunk_hub[c + 1]);
+        for (uint32_t b = p.chunk_blk[c]; b < p.chunk_blk[c + 1]; ++b) REQUIRE(p.blk_row[b] >= ch[c] && p.blk_row[b + 1] <= ch[c + 1]);
+        for (uint32_t h = p.chunk_hub[c]; h < p.chunk_hub[c + 1]; ++h) REQUIRE(p.hub_row[h] >= ch[c] && p.hub_row[h] < ch[c + 1]);
+    }
+    return 0;
+}
+
+struct plan_case { u32s deg, chunks, blk_row, blk_e0, hub_row, hub_blk, chunk_blk, chunk_hub; };
+
+static int test_segment_plan(const char *dataset) {
+    // cap 4, rcap 3; the tables are worked out by hand
+    const plan_case cases[] = {
+        {{0}, {}, {0, 1}, {0, 0}, {}, {}, {0, 1}, {0, 0}},
+        {{0, 0, 0, 0}, {}, {0, 3, 4}, {0, 0, 0}, {}, {}, {0, 2}, {0, 0}},                        // the row limit splits at 3
+        {{4}, {}, {0, 1}, {0, 4}, {}, {}, {0, 1}, {0, 0}},                                       // exactly cap: no hub
+        {{5}, {}, {0, 1}, {0, 5}, {0}, {0}, {0, 1}, {0, 1}},
+        {{5, 1, 1}, {}, {0, 1, 3}, {0, 5, 7}, {0}, {0}, {0, 2}, {0, 1}},                         // a hub first
+        {{1, 1, 5}, {}, {0, 2, 3}, {0, 2, 7}, {2}, {1}, {0, 2}, {0, 1}},                         // a hub last
+        {{5, 6}, {}, {0, 1, 2}, {0, 5, 11}, {0, 1}, {0, 1}, {0, 2}, {0, 2}},                     // adjacent hubs
+        {{2, 2, 1}, {}, {0, 2, 3}, {0, 4, 5}, {}, {}, {0, 2}, {0, 0}},                           // the edge limit splits after two rows
+        {{1, 1, 1, 1, 5, 1}, {}, {0, 3, 4, 5, 6}, {0, 3, 4, 9, 10}, {4}, {2}, {0, 4}, {0, 1}},
+        {{1, 1, 1, 1, 5, 1}, {0, 2, 6}, {0, 2, 4, 5, 6}, {0, 2, 4, 9, 10}, {4}, {2}, {0, 1, 4}, {0, 0, 1}},        // a boundary inside a would-be segment
+        {{1, 1, 1, 1, 5, 1}, {0, 0, 6}, {0, 3, 4, 5, 6}, {0, 3, 4, 9, 10}, {4}, {2}, {0, 0, 4}, {0, 0, 1}},        // an empty leading chunk
+        {{1, 1, 1, 1, 5, 1}, {0, 6, 6}, {0, 3, 4, 5, 6}, {0, 3, 4, 9, 10}, {4}, {2}, {0, 4, 4}, {0, 1, 1}},        // an empty trailing chunk
+        {{1, 1, 1, 1, 5, 1}, {0, 4, 5, 6}, {0, 3, 4, 5, 6}, {0, 3, 4, 9, 10}, {4}, {2}, {0, 2, 3, 4}, {0, 0, 1, 1}},  // boundaries around the hub
+    };
+    for (const plan_case &c : cases) {
+        std::vector<uint64_t> rp(c.deg.size() + 1, 0);
+        for (size_t i = 0; i < c.deg.size(); ++i) rp[i + 1] = rp[i] + c.deg[i];
+        sbmbp::segment_plan_t p;
+        REQUIRE(check_plan(rp, uint32_t(c.deg.size()), 4, 3, c.chunks, p) == 0);
+        REQUIRE(p.blk_row == c.blk_row && p.blk_e0 == c.blk_e0 && p.hub_row == c.hub_row && p.hub_blk == c.hub_blk);
+        REQUIRE(p.chunk_blk == c.chunk_blk && p.chunk_hub == c.chunk_hub);
+    }
+    {   // no rows at all: one empty chunk, no segment
+        const std::vector<uint64_t> rp{0};
+        sbmbp::segment_plan_t p;
+        REQUIRE(check_plan(rp, 0, 4, 3, {}, p) == 0);
+        REQUIRE(p.blk_row == u32s{0} && p.hub_row.empty() && p.chunk_blk == (u32s{0, 0}));
+    }
+    // the shipped graphs at the caps of the Q <= 2 frame, whole and in chunks
+    const std::string dir = std::string(dataset).substr(0, std::string(dataset).find_last_of('/') + 1);
+    for (const char *name : {"c1_dataset.edgelist", "hub_n600.edgelist"}) {
+        std::vector<uint32_t> pairs;
+        REQUIRE(sbmbp::read_edgelist((dir + name).c_str(), pairs) == 0);
+        uint32_t n = 0;
+        for (uint32_t v : pairs) n = std::max(n, v + 1);
+        sbmbp_graph g;
+        REQUIRE(sbmbp::graph_from_pairs(g, pairs.data(), pairs.size() / 2, n) == 0);
+        sbmbp::segment_plan_t p;
+        REQUIRE(check_plan(g.row_ptr, g.n, 256, 128, {}, p) == 0);
+        REQUIRE(check_plan(g.row_ptr, g.n, 256, 128, {0, g.n / 3, g.n / 3, g.n - 1, g.n}, p) == 0);
+        REQUIRE(check_plan(g.row_ptr, g.n, 64, 64, {0, g.n / 2, g.n}, p) == 0);  // (the Q 9..16 frame: hub_n600's rows of 102, 80, 71 edges are hubs)
+        REQUIRE(p.hub_row.empty() == (g.max_degree <= 64));
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ batch planner
+static int test_planner() {
+    using sbmbp::batch_planner;
+    {
+        batch_planner p(4, 1e-3);
+        REQUIRE(p.next == 4);
+        p.step(0.1, 2, 2);
+        REQUIRE(p.next == 4);  // the first reading: nothing to compare with
+        p.step(0.025, 4, 4);   // rate 0.5 per sweep, 0.025 -> 1e-3 needs ceil(4.64) = 5 more, none queued ahead
+        REQUIRE(p.next == 4 && p.prev_md == 0.025 && p.prev_idx == 4);
+    }
+    {
+        batch_planner p(8, 1e-3);
+        p.step(0.1, 2, 2);
+        p.step(0.025, 4, 8);  // 4 queued ahead of the reading: 5 - 4
+        REQUIRE(p.next == 1);
+        p.step(0.025, 5, 9);  // a reading that did not fall
+        REQUIRE(p.next == 8 && p.prev_idx == 5);
+        p.step(0.0, 6, 10);   // no difference reported: the previous reading stays
+        REQUIRE(p.next == 8 && p.prev_md == 0.025 && p.prev_idx == 5);
+        p.step(0.0005, 7, 10);  // already below the criterion
+        REQUIRE(p.next == 1);
+        p.reset();
+        REQUIRE(p.next == 8 && p.prev_md == -1.0);
+    }
+    for (double crit : {0.0, -1.0}) {  // a criterion that is not positive
+        batch_planner p(8, crit);
+        p.step(0.1, 2, 2);
+        p.step(0.025, 4, 8);
+        REQUIRE(p.next == 8);
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ the loops over fakes
+struct shared_driver {
+    static std::string planned(fakes::device &dev, double crit, uint32_t max_sweeps, uint32_t batch_max, bool psi_ok, bool first_explicit) {
+        fakes::state cs{0.0, -1, 0, 0, 0};
+        uint32_t psi = 0;
+        sbmbp::batch_planner plan(std::max<uint32_t>(1, batch_max), crit);
+        const int rc = sbmbp::converge_run(
+            max_sweeps, plan, psi_ok, first_explicit,
+            [&](int slot, uint32_t first, uint32_t n, bool form_psi) {
+                for (uint32_t j = first; j < first + n; ++j) dev.sweep(j, form_psi && !(j == 0 && first_explicit));
+                return dev.record(slot);
+            },
+            [&](int slot, fakes::state *st) {
+                const int w = dev.wait(slot);
+                if (w == 0) *st = dev.slots[slot][0];
+                return w;
+            },
+            [&]() { return dev.resume(); }, &cs, &psi);
+        return dev.end(rc, psi, plan.next, {cs});
+    }
+    static std::string fixed(fakes::device &dev, uint32_t max_sweeps, uint32_t batch_max) {
+        std::vector<fakes::state> cs(dev.cur.size(), fakes::state{0.0, -1, 0, 0, 0});
+        uint32_t done = 0;
+        const int rc = sbmbp::queue_ahead(
+            max_sweeps, done,
+            [&](int slot) {
+                const uint32_t n = std::min(batch_max, max_sweeps - done);
+                for (uint32_t k = 0; k < n; ++k) dev.sweep(done + k, false);
+                done += n;
+                return dev.record(slot);
+            },
+            [&](int slot, bool *stopped) {
+                const int w = dev.wait(slot);
+                if (w != 0) return w;
+                cs = dev.slots[slot];
+                *stopped = std::all_of(cs.begin(), cs.end(), [](const fakes::state &s) { return s.stop != 0; });
+                return 0;
+            });
+        return dev.end(rc, 0, batch_max, cs);
+    }
+    struct front {
+        fakes::em_front &fe;
+        uint32_t R;
+        int converge(const double *crit, const uint8_t *active, uint32_t *executed) {
+            for (uint32_t r = 0; r < R; ++r) executed[r] = active[r] ? fe.converge(r, crit[r]) : 0;
+            return 0;
+        }
+        int expect(const uint8_t *active, double *na_e, double *, double *cab_e, double *f) {
+            for (uint32_t r = 0; r < R; ++r) if (active[r]) f[r] = fe.expect(r, na_e + size_t(r) * fe.Q, cab_e + size_t(r) * fe.Q * fe.Q);
+            return 0;
+        }
+        void params(uint32_t r, std::vector<uint32_t> &na, std::vector<double> &cab) { na = fe.na[r]; cab = fe.cab[r]; }
+        int apply(uint32_t r, const uint32_t *na, const double *cab) { fe.apply(r, na, cab); return 0; }
+        int finish(uint32_t r) { mix_at_finish = *mix; fe.finish(r); return 0; }
+        const double *mix;
+        double mix_at_finish;
+    };
+    static std::string em(fakes::em_front &fe, float crit, uint32_t max_time, double lr) {
+        double field_mix = 1.0;
+        const uint32_t R = uint32_t(fe.f.size());
+        std::vector<fakes::em_result> out(R);
+        front f{fe, R, &field_mix, -1.0};
+        const int rc = sbmbp::em_loop(f, R, fe.Q, fe.N, crit, max_time, double(float(lr)), 1.0, field_mix, 0.3, out.data());
+        return fakes::em_end(fe, rc, out, f.mix_at_finish, field_mix);
+    }
+};
+
+static int test_loops() {
+    static const char *const expected[] = {
+#include "parent_traces.inc"
+    };
+    const std::vector<std::string> got = fakes::run_cases<shared_driver>();
+    REQUIRE(got.size() == sizeof expected / sizeof expected[0]);
+    for (size_t i = 0; i < got.size(); ++i)
+        if (got[i] != expected[i]) {
+            std::fprintf(stderr, "host_sanitize: loop case %zu\n  got      %s\n  expected %s\n", i, got[i].c_str(), expected[i]);
+            return 1;
+        }
+    // what the recorded traces say, spelled out for the cases that matter most (so that a wrong recording cannot pass either)
+    const auto head = [&](size_t i) { return got[i].substr(0, got[i].find(" |")); };
+    REQUIRE(head(0).empty() && head(10).empty());                                     // max_sweeps = 0 queues nothing
+    REQUIRE(head(1) == " s0m r0 w0");                                                 // one queue, one wait, no drain
+    REQUIRE(head(2) == " s0m s1m r0 s2m s3m r1 w0 s4m r0 w1 w0");                     // 2, 2, 1 on slots 0, 1, 0
+    REQUIRE(got[2].find("inflight=2") != std::string::npos);
+    REQUIRE(head(3) == " s0m s1m r0 s2m s3m r1 w0 s4m s5m r0 w1 w0");                 // the stop shows in slot 1: one more wait, on slot 0
+    REQUIRE(got[3].find("[3,1,0,3,") != std::string::npos);
+    REQUIRE(head(4) == head(2));                                                      // a stop in the final batch: no further wait
+    REQUIRE(head(15) == " s0p s1p s2p r0 s3p s4p s5p r1 w0 w1 R s3m s4m s5m r0 s6m s7m s8m r1 w0 s9m r0 w1 w0");
+    REQUIRE(got[15].find("psi=3 next=3") != std::string::npos && got[15].find("[10,0,0,") != std::string::npos);
+    REQUIRE(head(7) == " s0m s1m r0 s2m s3m r1" && head(8) == " s0m s1m r0 s2m s3m r1 w0" && head(9) == " s0m s1m r0");  // errors end it at once
+    for (size_t i : {7, 8, 9, 19, 20}) REQUIRE(got[i].find("rc=7") != std::string::npos);
+    REQUIRE(got[22].find("[1,1,-1.5,7]") != std::string::npos);                       // constant: status 1 after one step; 3 + 4 sweeps
+    REQUIRE(got[23].find(" A") == std::string::npos && got[23].find("[0,2,nan,3]") != std::string::npos);
+    REQUIRE(got[24].find(" A") == std::string::npos && got[24].find("[0,2,inf,3]") != std::string::npos);
+    REQUIRE(got[25].find("[6,0,6,33]") != std::string::npos);                         // out of steps: status 0, em_steps = max_time
+    REQUIRE(got[26].find(" C0:" + fakes::num(double(float(2.0 * 0.1)))) == 0);        // tightened before the first run
+    REQUIRE(head(27) == " F0" && got[27].find("[0,0,0,0]") != std::string::npos);     // no round, one finish
+    const auto result = [&](size_t i, size_t k) {  // the k-th [..] group of case i
+        size_t at = got[i].find(" |");
+        for (size_t x = 0; x <= k; ++x) at = got[i].find('[', at + 1);
+        return got[i].substr(at, got[i].find(']', at) - at + 1);
+    };
+    for (size_t r = 0; r < 3; ++r) REQUIRE(result(28, r) == result(29 + r, 0));        // in a batch as alone
+    REQUIRE(head(28).rfind(" C0:") == head(28).find(" C0:", 10) && head(28).find(" E0", head(28).find(" A1:53")) == std::string::npos);  // an ended run is left alone
+    for (size_t i = 22; i < got.size(); ++i) REQUIRE(got[i].find("mix=" + fakes::num(0.3) + "/1 ") != std::string::npos);  // lowered until the last finish, then restored
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: host_sanitize <edge list of the shipped data set>\n"); return 2; }
-    const int rc = run(argv[1]);
+    int rc = run(argv[1]);
+    if (rc == 0) rc = test_segment_plan(argv[1]);
+    if (rc == 0) rc = test_planner();
+    if (rc == 0) rc = test_loops();
     if (rc == 0) std::printf("host_sanitize ok\n");
     return rc;
 }
