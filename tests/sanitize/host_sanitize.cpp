@@ -262,6 +262,32 @@ static int test_segment_plan(const char *dataset) {
     return 0;
 }
 
+// Plans worked out elsewhere (tests/boundary_graph.py segment_model on the boundary graphs): per plan one line
+// `cap rcap n n_bounds n_hubs`, then the n degrees, the segment boundaries and the hub rows. segment_plan must give exactly
+// these, and pass its invariants.
+static int test_plans_from_file(const char *path, size_t *count) {
+    std::ifstream f(path);
+    REQUIRE(f.good());
+    uint32_t cap, rcap, n, nb, nh;
+    for (*count = 0; f >> cap >> rcap >> n >> nb >> nh; ++*count) {
+        u32s deg(n), bounds(nb), hubs(nh);
+        for (u32s *v : {&deg, &bounds, &hubs}) for (uint32_t &x : *v) REQUIRE(bool(f >> x));
+        std::vector<uint64_t> rp(size_t(n) + 1, 0);
+        for (uint32_t i = 0; i < n; ++i) rp[i + 1] = rp[i] + deg[i];
+        sbmbp::segment_plan_t p;
+        REQUIRE(check_plan(rp, n, cap, rcap, {}, p) == 0);
+        if (p.blk_row != bounds || p.hub_row != hubs) {
+            std::fprintf(stderr, "host_sanitize: plan %zu (cap %u, rcap %u, %u rows): segment_plan gives %zu segments and %zu hub rows, the file %zu and %zu\n",
+                         *count, cap, rcap, n, p.blk_row.size() - 1, p.hub_row.size(), bounds.size() - 1, hubs.size());
+            for (size_t b = 0; b < std::min(p.blk_row.size(), bounds.size()); ++b)
+                if (p.blk_row[b] != bounds[b]) { std::fprintf(stderr, "  first difference: boundary %zu is row %u, the file says %u\n", b, p.blk_row[b], bounds[b]); break; }
+            return 1;
+        }
+    }
+    REQUIRE(f.eof() && *count > 0);
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------ batch planner
 static int test_planner() {
     using sbmbp::batch_planner;
@@ -405,7 +431,13 @@ static int test_loops() {
 }
 
 int main(int argc, char **argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: host_sanitize <edge list of the shipped data set>\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: host_sanitize <edge list of the shipped data set> [--plans <file>]\n"); return 2; }
+    if (argc == 4 && std::strcmp(argv[2], "--plans") == 0) {  // the plan comparison alone
+        size_t count = 0;
+        const int prc = test_plans_from_file(argv[3], &count);
+        if (prc == 0) std::printf("host_sanitize ok: %zu plans\n", count);
+        return prc;
+    }
     int rc = run(argv[1]);
     if (rc == 0) rc = test_segment_plan(argv[1]);
     if (rc == 0) rc = test_planner();
