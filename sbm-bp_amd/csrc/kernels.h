@@ -585,6 +585,10 @@ __device__ __forceinline__ void edge_field(const dev_params *__restrict__ P, con
 // ------------------------------------------------------------------------------------------------
 // K1: one synchronous sweep over the rows of this workgroup's segment.
 // partials[b*(Q+1) + q] = sum_rows g_i psi_i[q],  partials[b*(Q+1)+Q] = max |delta message|.
+// The body (three phases, the exact-cavity fallback, the probe sweep) is sweep_msg_body.inc, which k_sweep_batch
+// (kernels_batch.h) includes as well: one definition, two kernels. It is included as text between the braces, with hooks
+// where the batch forms a replica's pointers (none are needed here), because the same body as an inlined __device__
+// function compiles to other code in every instantiation, and the include does not.
 // ------------------------------------------------------------------------------------------------
 template <int Q> struct sweep_waves { static constexpr int N = Q == 16 ? 2 : 1; };  // register target, see k_sweep_psi (Q = 16: 258 - 265 registers otherwise)
 template <int Q, bool DC2>
@@ -593,193 +597,17 @@ k_sweep(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ rev, 
         const double *__restrict__ Mold, double *__restrict__ Mnew, const double *__restrict__ psi_old,
         double *__restrict__ psi, const int32_t *__restrict__ clamp, const uint32_t *__restrict__ blk_row,
         const uint32_t *__restrict__ blk_e0, const dev_params *__restrict__ P, int dc, double damp, double *__restrict__ partials) {
-    constexpr int EPT = frame_cfg<Q>::EPT, CAP = frame_cfg<Q>::CAP, RCAP = frame_cfg<Q>::RCAP;
-    __shared__ double sb[CAP * Q];     // b_e[q] of every edge of the segment
-    __shared__ double sA[RCAP * Q];    // unnormalised marginal of every row
-    __shared__ uint32_t srp[RCAP + 1]; // row offsets relative to the segment
-    __shared__ uint16_t srow[CAP];     // row (within segment) of every edge
-    __shared__ uint8_t sfl[RCAP];      // 1 = clamped row
-    __shared__ double sred[frame_cfg<Q>::WAVES * (Q + 1)];
-    __shared__ int sbig;               // the segment holds a row above BIG_ROW edges
-
-    // bounds and stop flag from one level of scalar loads; streams issued before the row offsets -> LDS fill
-    const int tid = threadIdx.x;
-    const int stop = P->stop;
-    const uint32_t r0 = blk_row[blockIdx.x], r1 = blk_row[blockIdx.x + 1];
-    const uint32_t e0 = blk_e0[blockIdx.x];
-    const int nrows = int(r1 - r0), ne = int(blk_e0[blockIdx.x + 1] - e0);
-    if (stop || ne > CAP) return;  // stopped run, or hub row (the fragment kernels own it): uniform exit before any barrier
-
-    // ---- phase 1: lane per directed edge: gather incoming message, b = W^T m -> LDS (branch-free loads,
-    // see k_sweep_psi)
-    constexpr int RPT = RCAP / frame_cfg<Q>::TPB + 1;
-    double mo[EPT][Q];
-    uint32_t rk[EPT], kk[EPT];
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) {
-        const int le = j * frame_cfg<Q>::TPB + tid;
-        kk[j] = (ne > 0) ? e0 + uint32_t(le < ne ? le : 0) : 0u;
-    }
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) rk[j] = load_idx_stream(rev + kk[j]);
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) load_msg_stream<Q>(Mold, kk[j], mo[j]);
-    uint32_t rpv[RPT];
-#pragma unroll
-    for (int t = 0; t < RPT; ++t) { const int r = tid + t * frame_cfg<Q>::TPB; rpv[t] = row_ptr[r0 + uint32_t(r < nrows ? r : nrows)]; }
-    double mi[EPT][Q];
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) load_msg<Q>(Mold, rk[j], mi[j]);
-    if (tid == 0) sbig = 0;
-#pragma unroll
-    for (int t = 0; t < RPT; ++t) { const int r = tid + t * frame_cfg<Q>::TPB; if (r <= nrows) srp[r] = rpv[t] - e0; }
-    __syncthreads();  // srp visible
-    for (int r = tid; r < nrows; r += frame_cfg<Q>::TPB) {
-        const int es = int(srp[r]), ee = int(srp[r + 1]);
-        if (ee - es > BIG_ROW) sbig = 1;
-        for (int e = es; e < ee; ++e) srow[e] = uint16_t(r);
-        sfl[r] = (clamp != nullptr && clamp[r0 + r] != -1) ? 1 : 0;
-    }
-    if (DC2) __syncthreads();  // per-edge weights need the edge -> row map
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) {
-        const int le = j * frame_cfg<Q>::TPB + tid;
-        if (le < ne) {
-            double didl = 0.0;
-            if (DC2) {
-                const int r = srow[le];
-                const uint32_t l = nbr[e0 + le];
-                didl = double(srp[r + 1] - srp[r]) * double(ndeg[l]);
-            }
-            double b[Q];
-            edge_field<Q, DC2>(P, mi[j], didl, b);
-            store_vec<Q>(&sb[le * Q], b);
-        }
-    }
-    __syncthreads();
-
-    // ---- phase 2: lane per row (a wave per row above BIG_ROW edges): A[q] = prod_e b_e[q];
-    //      psi_i = normalise(A * eta * F_i)
-    double Sacc[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) Sacc[q] = 0.0;
-    auto finish_row = [&](int r, double di, double (&A)[Q], const int *ae /* per-component exponents of a long row, or null */,
-                          const double *ft = nullptr /* the row's line of P->ftab (rows of <= FT_D edges under dc), or null */) {
-        double pv[Q];
-        double tot;
-        if (ae) {
-            int x[Q];
-#pragma unroll
-            for (int q = 0; q < Q; ++q) x[q] = ae[q];
-            tot = apply_field_x<Q>(P, dc, di, A, x);
-        } else {
-            tot = apply_field<Q>(P, dc, di, A, ft);
-        }
-        store_vec<Q>(&sA[r * Q], A);
-        const double inv = 1.0 / tot;
-        const double gi = dc ? di : 1.0;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) { pv[q] = A[q] * inv; Sacc[q] += gi * pv[q]; }
-        store_vec<Q>(psi + size_t(r0 + r) * Q, pv);
-    };
-    for (int r = tid; r < nrows; r += frame_cfg<Q>::TPB) {
-        const int es = int(srp[r]), ee = int(srp[r + 1]);
-        const double di = double(ee - es);
-        if (sfl[r]) {  // clamped: marginal and out-messages stay as initialised (bp.cpp:1115-1124)
-            double pv[Q];
-            load_vec<Q>(psi_old + size_t(r0 + r) * Q, pv);
-            store_vec<Q>(psi + size_t(r0 + r) * Q, pv);
-            const double gi = dc ? di : 1.0;
-#pragma unroll
-            for (int q = 0; q < Q; ++q) Sacc[q] += gi * pv[q];
-        } else if (ee - es <= BIG_ROW) {
-            double A[Q], ft[Q];
-            const bool tab = dc != 0 && ee - es <= FT_D;  // the field factors of this degree: loaded while the product runs
-            if (tab) load_vec<Q>(P->ftab + size_t(ee - es) * QMAX, ft);
-#pragma unroll
-            for (int q = 0; q < Q; ++q) A[q] = 1.0;
-            for (int e = es; e < ee; ++e) {
-                double b[Q];
-                load_vec<Q>(&sb[e * Q], b);
-#pragma unroll
-                for (int q = 0; q < Q; ++q) A[q] *= b[q];
-                rescale_pow2<Q>(A);
-            }
-            finish_row(r, di, A, nullptr, tab ? ft : nullptr);
-        }
-    }
-    if (sbig)  // uniform: written before the barrier that ends phase 1
-    for (int r = tid >> 6; r < nrows; r += frame_cfg<Q>::WAVES) {  // wave-uniform row index
-        const int es = int(srp[r]), ee = int(srp[r + 1]);
-        if (ee - es > BIG_ROW && !sfl[r]) {
-            double A[Q];
-            int ae[Q];
-            row_product_wave<Q>(sb, es, ee, A, ae);
-            if ((tid & 63) == 0) finish_row(r, double(ee - es), A, ae);
-        }
-    }
-    __syncthreads();
-
-    // ---- phase 3: lane per directed edge: cavity, normalise, damp, store
-    double md = 0.0;
-    const int probe2 = P->ar_probe2;  // adaptive relaxation's probe sweep: report |m^{t+1} - m^{t-1}| (m^{t-1} sits in the slot written below)
-    damp *= P->damp_auto;
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) {
-        const int le = j * frame_cfg<Q>::TPB + tid;
-        if (le < ne) {
-            const int r = srow[le];
-            double out[Q];
-            if (sfl[r]) {
-#pragma unroll
-                for (int q = 0; q < Q; ++q) out[q] = mo[j][q];
-            } else {
-                double A[Q], b[Q], cav[Q];
-                load_vec<Q>(&sA[r * Q], A);
-                load_vec<Q>(&sb[le * Q], b);
-                bool ok = true;
-                double tot = 0.0;
-#pragma unroll
-                for (int q = 0; q < Q; ++q) {
-                    cav[q] = A[q] / b[q];
-                    ok = ok && (b[q] > 0.0) && (cav[q] <= 1.7e308);
-                    tot += cav[q];
-                }
-                if (!ok) {  // exact cavity product when a division is unusable (b == 0 or overflow)
-                    const int es = int(srp[r]), ee = int(srp[r + 1]);
-                    const double di = double(ee - es);
-                    int ce[Q];
-#pragma unroll
-                    for (int q = 0; q < Q; ++q) { cav[q] = 1.0; ce[q] = 0; }
-                    for (int e = es; e < ee; ++e) {
-                        if (e == le) continue;
-#pragma unroll
-                        for (int q = 0; q < Q; ++q) cav[q] *= sb[e * Q + q];
-                        x_norm<Q>(cav, ce);
-                    }
-                    tot = apply_field_x<Q>(P, dc, di, cav, ce);
-                }
-                const double inv = 1.0 / tot;
-                double ref[Q];
-                if (probe2) {  // uniform
-                    load_msg<Q>(Mnew, size_t(e0 + le), ref);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < Q; ++q) ref[q] = mo[j][q];
-                }
-#pragma unroll
-                for (int q = 0; q < Q; ++q) {
-                    const double nv = cav[q] * inv;
-                    out[q] = damp * nv + (1.0 - damp) * mo[j][q];
-                    // 1-step: against the undamped value (bp.cpp:1059-1063); the probe compares what is stored, and a damped
-                    // message moves by damp * (new - old) per sweep, so it is scaled back to compare like with like
-                    md = nanmax(md, probe2 ? fabs(ref[q] - out[q]) / damp : fabs(ref[q] - nv));
-                }
-            }
-            store_msg_stream<Q>(Mnew, size_t(e0 + le), out);
-        }
-    }
-    block_reduce_store<Q, frame_cfg<Q>::WAVES>(Sacc, md, sred, partials + size_t(blockIdx.x) * (Q + 1));
+#define SWEEP_REPLICA
+#define SWEEP_MOLD
+#define SWEEP_PSI
+#define SWEEP_MNEW
+#define SWEEP_RECORD partials + size_t(blockIdx.x) * (Q + 1)
+#include "sweep_msg_body.inc"
+#undef SWEEP_REPLICA
+#undef SWEEP_MOLD
+#undef SWEEP_PSI
+#undef SWEEP_MNEW
+#undef SWEEP_RECORD
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1424,6 +1252,22 @@ k_hub_frag_product(const uint32_t *__restrict__ row_ptr, const uint32_t *__restr
         for (int q = 0; q < Q; ++q) { hf.pA[size_t(f) * Q + q] = A[q]; hf.pE[size_t(f) * Q + q] = ae[q]; }
     }
 }
+// The close of the cavity kernels of the hub rows (k_hub_frag_cavity, k_hub_frag_cavity_msg, k_hub_step_cavity). Their other
+// common piece, the fold of the fragment products into the row's marginal, stays written out in each.
+// Sticky-NaN maximum of md over the BLOCK-wide workgroup, met with the row's other fragments in *slot (a non-negative double,
+// or a NaN, orders like its bit pattern); smd holds BLOCK / 64 doubles
+__device__ __forceinline__ void block_nanmax_atomic(double md, double *smd, double *slot) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) md = nanmax(md, __shfl_xor(md, o, 64));
+    if ((tid & 63) == 0) smd[tid >> 6] = md;
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 1; w < BLOCK / 64; ++w) md = nanmax(md, smd[w]);
+        atomicMax(reinterpret_cast<unsigned long long *>(slot), (unsigned long long)__double_as_longlong(fabs(md)));
+    }
+}
 template <int Q>
 __global__ void __launch_bounds__(BLOCK)
 k_hub_frag_cavity(const uint32_t *__restrict__ row_ptr, double *__restrict__ Mio, const double *__restrict__ psi_old,
@@ -1487,15 +1331,7 @@ k_hub_frag_cavity(const uint32_t *__restrict__ row_ptr, double *__restrict__ Mio
         }
         store_msg<Q>(Mio, size_t(e0 + le), out);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) md = nanmax(md, __shfl_xor(md, o, 64));
-    if ((tid & 63) == 0) smd[tid >> 6] = md;
-    __syncthreads();
-    if (tid == 0) {
-#pragma unroll
-        for (int w = 1; w < BLOCK / 64; ++w) md = nanmax(md, smd[w]);
-        atomicMax(reinterpret_cast<unsigned long long *>(rec + Q), (unsigned long long)__double_as_longlong(fabs(md)));
-    }
+    block_nanmax_atomic(md, smd, rec + Q);
 }
 
 // gather rows idx[0..n) of a [rows][Q] table into a contiguous buffer (halo send packing). With
@@ -1656,21 +1492,24 @@ k_hub_frag_cavity_msg(const uint32_t *__restrict__ row_ptr, const double *__rest
         }
         store_msg<Q>(Mnew, size_t(e0 + le), out);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) md = nanmax(md, __shfl_xor(md, o, 64));
-    if ((tid & 63) == 0) smd[tid >> 6] = md;
-    __syncthreads();
-    if (tid == 0) {
-#pragma unroll
-        for (int w = 1; w < BLOCK / 64; ++w) md = nanmax(md, smd[w]);
-        atomicMax(reinterpret_cast<unsigned long long *>(rec + Q), (unsigned long long)__double_as_longlong(fabs(md)));
-    }
+    block_nanmax_atomic(md, smd, rec + Q);
 }
 
 // ------------------------------------------------------------------------------------------------
 // sum_i g_i psi_i[q] over row chunks (init_h, belief_propagation.cpp:320-332); chunk c covers rows
 // [c*rows_per_blk, ...). Writes partials[c*(Q+1) + q]; slot Q (max) = 0.
 // ------------------------------------------------------------------------------------------------
+// S += g_i psi_i, g_i the degree under dc and 1 otherwise: row i's term of the field sums (k_psi_sum, k_psi_sum_batch). The
+// chunk loop around it stays in the two kernels (register counts: DESIGN.md section 8)
+template <int Q>
+__device__ __forceinline__ void psi_row_add(const uint32_t *__restrict__ row_ptr, const double *__restrict__ psi, uint32_t i, int dc,
+                                            double (&S)[Q]) {
+    double pv[Q];
+    load_vec<Q>(psi + size_t(i) * Q, pv);
+    const double gi = dc ? double(row_ptr[i + 1] - row_ptr[i]) : 1.0;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) S[q] += gi * pv[q];
+}
 template <int Q>
 __global__ void __launch_bounds__(BLOCK)
 k_psi_sum(const uint32_t *__restrict__ row_ptr, const double *__restrict__ psi, uint32_t n_rows, uint32_t rows_per_blk,
@@ -1681,13 +1520,7 @@ k_psi_sum(const uint32_t *__restrict__ row_ptr, const double *__restrict__ psi, 
     for (int q = 0; q < Q; ++q) S[q] = 0.0;
     const uint32_t lo = blockIdx.x * rows_per_blk;
     const uint32_t hi = min(n_rows, lo + rows_per_blk);
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += BLOCK) {
-        double pv[Q];
-        load_vec<Q>(psi + size_t(i) * Q, pv);
-        const double gi = dc ? double(row_ptr[i + 1] - row_ptr[i]) : 1.0;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) S[q] += gi * pv[q];
-    }
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += BLOCK) psi_row_add<Q>(row_ptr, psi, i, dc, S);
     block_reduce_store<Q>(S, 0.0, sred, partials + size_t(blockIdx.x) * (Q + 1));
 }
 
@@ -2255,9 +2088,9 @@ k_nonedge_adj(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__
 // (T = Q + Q^2 + ... + Q^K entries). Each workgroup stages a chunk of rows in LDS; thread t owns
 // tensor entries t, t+256, ...; partial tensors per workgroup are folded by k_fold_columns.
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(BLOCK)
-k_moments(const double *__restrict__ psi, uint32_t n_rows, int Q, int K, uint32_t rows_per_blk, int T,
-          double *__restrict__ partials /* [gridDim.x][T] */) {
+// the body of k_moments and k_moments_batch: `out` is this workgroup's [T] row of partials, psi the marginal table it reads
+__device__ __forceinline__ void moments_chunk(const double *__restrict__ psi, uint32_t n_rows, int Q, uint32_t rows_per_blk, int T,
+                                              double *__restrict__ out) {
     __shared__ double sp[BLOCK * QMAX];
     __shared__ double scomb[BLOCK];
     const int tid = threadIdx.x;
@@ -2269,7 +2102,8 @@ k_moments(const double *__restrict__ psi, uint32_t n_rows, int Q, int K, uint32_
     const int sub = nsub > 1 ? tid / T : 0;
     const bool active = nsub == 1 || tid < nsub * T;
     const uint32_t lo = blockIdx.x * rows_per_blk, hi = min(n_rows, lo + rows_per_blk);
-    const uint32_t stage_rows = Q <= QMAX ? uint32_t(BLOCK) : uint32_t(BLOCK * QMAX / Q);  // (label counts above 16: fewer rows per stage)
+    // (label counts above 16: fewer rows per stage; a replica batch never has them)
+    const uint32_t stage_rows = Q <= QMAX ? uint32_t(BLOCK) : uint32_t(BLOCK * QMAX / Q);
     for (uint32_t base = lo; base < hi; base += stage_rows) {
         const uint32_t cnt = min(stage_rows, hi - base);
         __syncthreads();
@@ -2302,12 +2136,17 @@ k_moments(const double *__restrict__ psi, uint32_t n_rows, int Q, int K, uint32_
         if (tid < T) {
             double s = scomb[tid];
             for (int u = 1; u < nsub; ++u) s += scomb[u * T + tid];
-            partials[size_t(blockIdx.x) * T + tid] = s;
+            out[tid] = s;
         }
         return;
     }
     int j = 0;
-    for (int ent = tid; ent < T; ent += BLOCK, ++j) partials[size_t(blockIdx.x) * T + ent] = acc[j];
+    for (int ent = tid; ent < T; ent += BLOCK, ++j) out[ent] = acc[j];
+}
+__global__ void __launch_bounds__(BLOCK)
+k_moments(const double *__restrict__ psi, uint32_t n_rows, int Q, int K, uint32_t rows_per_blk, int T,
+          double *__restrict__ partials /* [gridDim.x][T] */) {
+    moments_chunk(psi, n_rows, Q, rows_per_blk, T, partials + size_t(blockIdx.x) * T);
 }
 
 // First stage of a two-stage fold of [rows][stride] partials: workgroup b reduces the contiguous
@@ -2371,6 +2210,41 @@ k_fold_rows_sum(const double *__restrict__ in, uint32_t rows, uint32_t cols, uin
 // with k_nonedge_adj. Tile = 256 rows i (one per lane) x 256 rows l staged in LDS.
 // partial[0] = sum log(psi_i^T P psi_l), P = (1-cab/N)^beta;  partial[1] = sum num/den (entropy).
 // ------------------------------------------------------------------------------------------------
+// one lane's pair loop of the exact non-edge sums: row i of psi against the cnt rows staged in sl. acc0 += sum_l log(psi_i^T P
+// psi_l); with want_entropy acc1 += sum_l num/den (k_nonedge_exact_batch passes a literal 0 and no cab, which removes that
+// half). The sums are two scalars and the staging stays in the kernels (register counts: DESIGN.md section 8)
+template <int Q>
+__device__ __forceinline__ void nonedge_pair_sums(const double *__restrict__ psi, uint32_t i, const double *sl, uint32_t cnt,
+                                                  const double *__restrict__ Pmat, const double *__restrict__ cab, double invN,
+                                                  int want_entropy, double &acc0, double &acc1) {
+    double pi[Q], v[Q], vn[Q], vd[Q];
+    load_vec<Q>(psi + size_t(i) * Q, pi);
+#pragma unroll
+    for (int q2 = 0; q2 < Q; ++q2) {  // v = P^T psi_i etc., so a pair costs Q FMAs
+        double a = 0.0, an = 0.0, ad = 0.0;
+#pragma unroll
+        for (int q1 = 0; q1 < Q; ++q1) {
+            a += Pmat[q1 * Q + q2] * pi[q1];
+            if (want_entropy) {
+                const double c = cab[q1 * Q + q2];
+                an += (c * invN) * log(c) * pi[q1];
+                ad += (1.0 - c * invN) * pi[q1];
+            }
+        }
+        v[q2] = a; vn[q2] = an; vd[q2] = ad;
+    }
+    for (uint32_t r = 0; r < cnt; ++r) {
+        double f = 0.0, num = 0.0, den = 0.0;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const double pl = sl[r * Q + q];
+            f += v[q] * pl;
+            if (want_entropy) { num += vn[q] * pl; den += vd[q] * pl; }
+        }
+        if (f != 0.0) acc0 += log(f);
+        if (want_entropy && num * den != 0.0) acc1 += num / den;
+    }
+}
 template <int Q>
 __global__ void __launch_bounds__(BLOCK)
 k_nonedge_exact(const double *__restrict__ psi /* rows i: n of them (a shard: its own rows) */, uint32_t n,
@@ -2385,35 +2259,7 @@ k_nonedge_exact(const double *__restrict__ psi /* rows i: n of them (a shard: it
     for (uint32_t x = threadIdx.x; x < cnt * Q; x += BLOCK) sl[x] = psi_l[size_t(l0) * Q + x];
     __syncthreads();
     double acc[NE_NP] = {0.0, 0.0};
-    if (i < n) {
-        double pi[Q], v[Q], vn[Q], vd[Q];
-        load_vec<Q>(psi + size_t(i) * Q, pi);
-#pragma unroll
-        for (int q2 = 0; q2 < Q; ++q2) {  // v = P^T psi_i etc., so a pair costs Q FMAs
-            double a = 0.0, an = 0.0, ad = 0.0;
-#pragma unroll
-            for (int q1 = 0; q1 < Q; ++q1) {
-                a += Pmat[q1 * Q + q2] * pi[q1];
-                if (want_entropy) {
-                    const double c = cab[q1 * Q + q2];
-                    an += (c * invN) * log(c) * pi[q1];
-                    ad += (1.0 - c * invN) * pi[q1];
-                }
-            }
-            v[q2] = a; vn[q2] = an; vd[q2] = ad;
-        }
-        for (uint32_t r = 0; r < cnt; ++r) {
-            double f = 0.0, num = 0.0, den = 0.0;
-#pragma unroll
-            for (int q = 0; q < Q; ++q) {
-                const double pl = sl[r * Q + q];
-                f += v[q] * pl;
-                if (want_entropy) { num += vn[q] * pl; den += vd[q] * pl; }
-            }
-            if (f != 0.0) acc[0] += log(f);
-            if (want_entropy && num * den != 0.0) acc[1] += num / den;
-        }
-    }
+    if (i < n) nonedge_pair_sums<Q>(psi, i, sl, cnt, Pmat, cab, invN, want_entropy, acc[0], acc[1]);
     block_reduce_store<NE_NP>(acc, 0.0, sred, partials + (size_t(blockIdx.y) * gridDim.x + blockIdx.x) * (NE_NP + 1));
 }
 
@@ -2467,6 +2313,29 @@ k_nonedge_exact_adj(const uint32_t *__restrict__ row_ptr, const uint32_t *__rest
 // accumulated per lane over a grid-stride loop, then folded. Output row per workgroup: Q*Q entries
 // (upper triangle filled). W' = cab (dc 0, no beta), cab (dc 1: prefactor cancels), x/(1+x) (dc 2).
 // ------------------------------------------------------------------------------------------------
+// per directed edge: its share of the Q (Q + 1) / 2 numerators (k_em_edges_batch, k_em_frame_batch). k_em_edges below holds
+// the same lines written out: edit the two in step
+template <int Q, bool DC2>
+__device__ __forceinline__ void em_edge_terms(const dev_params *__restrict__ P, const double (&mi)[Q], const double (&mo)[Q], double didl,
+                                              double (&acc)[Q * (Q + 1) / 2]) {
+    constexpr int T = Q * (Q + 1) / 2;
+    double term[T], norm_L = 0.0;
+    int t = 0;
+#pragma unroll
+    for (int q1 = 0; q1 < Q; ++q1) {
+#pragma unroll
+        for (int q2 = q1; q2 < Q; ++q2, ++t) {
+            double w = P->cab[q1 * Q + q2];
+            if (DC2) { double x = didl * w * P->invN; w = x / (1.0 + x); }
+            const double pr = (q1 == q2) ? (mi[q1] * mo[q2]) : (mi[q1] * mo[q2] + mi[q2] * mo[q1]);
+            term[t] = w * pr;
+            norm_L += term[t];
+        }
+    }
+    const double inv = 0.5 / norm_L;
+#pragma unroll
+    for (int u = 0; u < T; ++u) acc[u] += term[u] * inv;
+}
 template <int Q, bool DC2>
 __global__ void __launch_bounds__(BLOCK)
 k_em_edges(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ rev, const uint32_t *__restrict__ nbr, const uint32_t *__restrict__ ndeg /* degree of every table row (DC2 only) */,
@@ -2487,6 +2356,8 @@ k_em_edges(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ re
             const uint32_t i = src[k], l = nbr[k];
             didl = double(row_ptr[i + 1] - row_ptr[i]) * double(ndeg[l]);
         }
+        // em_edge_terms written out (the call costs this kernel registers: DESIGN.md section 8). The two are twins: a
+        // change to the weights, the pair products or the 0.5 / norm_L normalisation is made in both
         double term[T], norm_L = 0.0;
         int t = 0;
 #pragma unroll
@@ -2908,15 +2779,7 @@ k_hub_step_cavity(const uint32_t *__restrict__ row_ptr, double *M, double *psi, 
         }
         store_msg<Q>(M, size_t(e0 + le), out);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) md = nanmax(md, __shfl_xor(md, o, 64));
-    if ((tid & 63) == 0) smd[tid >> 6] = md;
-    __syncthreads();
-    if (tid == 0) {
-#pragma unroll
-        for (int w = 1; w < BLOCK / 64; ++w) md = nanmax(md, smd[w]);
-        atomicMax(reinterpret_cast<unsigned long long *>(rec + Q), (unsigned long long)__double_as_longlong(fabs(md)));
-    }
+    block_nanmax_atomic(md, smd, rec + Q);
 }
 
 // K2s (one workgroup, after every step): fixed-order fold of the step's records, S <- S + sum_step g_i (psi_new - psi_old),

@@ -4,10 +4,14 @@
 // graph. The batch keeps the graph tables once and the states replica-major in HBM:
 //     messages  [2][R][E2][Q-1]      marginals [2][R][N][Q]      dev_params P[R]      sweep records [R][n_segments][Q+1]
 // Replica r reads P[r]: its own cab / eta / beta, field, convergence state and adaptive-relaxation ladder. The sweep is the
-// synchronous sweep in the message-gather form with k_sweep's equations (kernels.h), built from the same device helpers;
+// synchronous sweep in the message-gather form, and it IS k_sweep's: both kernels include the one body in
+// sweep_msg_body.inc, and k_sweep_batch adds only where replica r's buffers start;
 // blockIdx.y is the replica, so the segment tables (row offsets, rev, under dc 2 nbr / ndeg) are read by R workgroups
 // that run side by side and share them in L2. A replica whose stop flag is set returns before any barrier: it costs an
 // empty workgroup and its state stays where its last sweep left it.
+// The same holds below the sweep: every batch kernel here is the replica's addressing, a call of the single engine's
+// __device__ rule in kernels.h (finalize_update, psi_row_add, em_edge_terms, moments_chunk, nonedge_pair_sums) and its
+// own final store. The stores stay apart because block_sum_store and block_reduce_store fold in different orders.
 #ifndef SBMBP_KERNELS_BATCH_H
 #define SBMBP_KERNELS_BATCH_H
 
@@ -32,6 +36,8 @@ struct batch_view {
 // K1b: sweep j of the current call over segment blockIdx.x of replica blockIdx.y. Replicas stop at different sweeps, so
 // the buffer a replica reads is its OWN parity par[r] moved on by j (a stopped replica executes nothing more in this call,
 // so the sweeps it did execute were sweeps 0 .. sweep_idx - 1 of the call).
+// The body is sweep_msg_body.inc, shared with k_sweep; the hooks below are all that is the batch's own. Included as text
+// and not called as a function: see the head of that file.
 // ------------------------------------------------------------------------------------------------
 template <int Q, bool DC2>
 __global__ void __launch_bounds__(frame_cfg<Q>::TPB) __attribute__((amdgpu_waves_per_eu(sweep_waves<Q>::N)))
@@ -40,198 +46,26 @@ k_sweep_batch(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__
               const uint32_t *__restrict__ blk_row, const uint32_t *__restrict__ blk_e0, double *__restrict__ Mall, double *__restrict__ psi_all,
               const dev_params *__restrict__ Pall, double *__restrict__ rec_all, const int *__restrict__ par_all, size_t msg_stride,
               size_t psi_stride, size_t rec_stride, uint32_t R, uint32_t j, int dc, double damp) {
-    constexpr int EPT = frame_cfg<Q>::EPT, CAP = frame_cfg<Q>::CAP, RCAP = frame_cfg<Q>::RCAP;
-    __shared__ double sb[CAP * Q];     // b_e[q] of every edge of the segment
-    __shared__ double sA[RCAP * Q];    // unnormalised marginal of every row
-    __shared__ uint32_t srp[RCAP + 1]; // row offsets relative to the segment
-    __shared__ uint16_t srow[CAP];     // row (within segment) of every edge
-    __shared__ uint8_t sfl[RCAP];      // 1 = clamped row
-    __shared__ double sred[frame_cfg<Q>::WAVES * (Q + 1)];
-    __shared__ int sbig;               // the segment holds a row above BIG_ROW edges
-
-    const int tid = threadIdx.x;
-    const uint32_t rep = blockIdx.y;
-    const dev_params *__restrict__ P = Pall + rep;
-    const int stop = P->stop;
-    const int par = par_all[rep];
-    const uint32_t r0 = blk_row[blockIdx.x], r1 = blk_row[blockIdx.x + 1];
-    const uint32_t e0 = blk_e0[blockIdx.x];
-    const int nrows = int(r1 - r0), ne = int(blk_e0[blockIdx.x + 1] - e0);
-    if (stop || ne > CAP) return;  // converged replica, or hub row (the fragment kernels own it): uniform exit before any barrier
-    const int mc = (par + int(j)) & 1;
-    // (the replica's other base pointers are formed where they are first needed, not held in scalar registers next to P's
+    // (the replica's base pointers are formed where they are first needed, not held in scalar registers next to P's
     // matrices through the whole kernel)
+#define SWEEP_REPLICA                                    \
+    const uint32_t rep = blockIdx.y;                     \
+    const dev_params *__restrict__ P = Pall + rep;       \
+    const int par = par_all[rep];
+#define SWEEP_MOLD                                       \
+    const int mc = (par + int(j)) & 1;                   \
     const double *__restrict__ Mold = Mall + (size_t(mc) * R + rep) * msg_stride;
-
-    // ---- phase 1: lane per directed edge: gather incoming message, b = W^T m -> LDS
-    constexpr int RPT = RCAP / frame_cfg<Q>::TPB + 1;
-    double mo[EPT][Q];
-    uint32_t rk[EPT], kk[EPT];
-#pragma unroll
-    for (int x = 0; x < EPT; ++x) {
-        const int le = x * frame_cfg<Q>::TPB + tid;
-        kk[x] = (ne > 0) ? e0 + uint32_t(le < ne ? le : 0) : 0u;
-    }
-#pragma unroll
-    for (int x = 0; x < EPT; ++x) rk[x] = load_idx_stream(rev + kk[x]);
-#pragma unroll
-    for (int x = 0; x < EPT; ++x) load_msg_stream<Q>(Mold, kk[x], mo[x]);
-    uint32_t rpv[RPT];
-#pragma unroll
-    for (int t = 0; t < RPT; ++t) { const int r = tid + t * frame_cfg<Q>::TPB; rpv[t] = row_ptr[r0 + uint32_t(r < nrows ? r : nrows)]; }
-    double mi[EPT][Q];
-#pragma unroll
-    for (int x = 0; x < EPT; ++x) load_msg<Q>(Mold, rk[x], mi[x]);
-    if (tid == 0) sbig = 0;
-#pragma unroll
-    for (int t = 0; t < RPT; ++t) { const int r = tid + t * frame_cfg<Q>::TPB; if (r <= nrows) srp[r] = rpv[t] - e0; }
-    __syncthreads();  // srp visible
-    for (int r = tid; r < nrows; r += frame_cfg<Q>::TPB) {
-        const int es = int(srp[r]), ee = int(srp[r + 1]);
-        if (ee - es > BIG_ROW) sbig = 1;
-        for (int e = es; e < ee; ++e) srow[e] = uint16_t(r);
-        sfl[r] = (clamp != nullptr && clamp[r0 + r] != -1) ? 1 : 0;
-    }
-    if (DC2) __syncthreads();  // per-edge weights need the edge -> row map
-#pragma unroll
-    for (int x = 0; x < EPT; ++x) {
-        const int le = x * frame_cfg<Q>::TPB + tid;
-        if (le < ne) {
-            double didl = 0.0;
-            if (DC2) {
-                const int r = srow[le];
-                const uint32_t l = nbr[e0 + le];
-                didl = double(srp[r + 1] - srp[r]) * double(ndeg[l]);
-            }
-            double b[Q];
-            edge_field<Q, DC2>(P, mi[x], didl, b);
-            store_vec<Q>(&sb[le * Q], b);
-        }
-    }
-    __syncthreads();
-
-    // ---- phase 2: lane per row (a wave per row above BIG_ROW edges): psi_i = normalise(prod_e b_e * eta * F_i)
-    const double *__restrict__ psi_old = psi_all + (size_t(mc) * R + rep) * psi_stride;
+#define SWEEP_PSI                                                                         \
+    const double *__restrict__ psi_old = psi_all + (size_t(mc) * R + rep) * psi_stride;  \
     double *__restrict__ psi = psi_all + (size_t(mc ^ 1) * R + rep) * psi_stride;
-    double Sacc[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) Sacc[q] = 0.0;
-    auto finish_row = [&](int r, double di, double (&A)[Q], const int *ae /* per-component exponents of a long row, or null */,
-                          const double *ft = nullptr /* the row's line of P->ftab, or null */) {
-        double pv[Q];
-        double tot;
-        if (ae) {
-            int x[Q];
-#pragma unroll
-            for (int q = 0; q < Q; ++q) x[q] = ae[q];
-            tot = apply_field_x<Q>(P, dc, di, A, x);
-        } else {
-            tot = apply_field<Q>(P, dc, di, A, ft);
-        }
-        store_vec<Q>(&sA[r * Q], A);
-        const double inv = 1.0 / tot;
-        const double gi = dc ? di : 1.0;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) { pv[q] = A[q] * inv; Sacc[q] += gi * pv[q]; }
-        store_vec<Q>(psi + size_t(r0 + r) * Q, pv);
-    };
-    for (int r = tid; r < nrows; r += frame_cfg<Q>::TPB) {
-        const int es = int(srp[r]), ee = int(srp[r + 1]);
-        const double di = double(ee - es);
-        if (sfl[r]) {  // clamped: marginal and out-messages stay as initialised
-            double pv[Q];
-            load_vec<Q>(psi_old + size_t(r0 + r) * Q, pv);
-            store_vec<Q>(psi + size_t(r0 + r) * Q, pv);
-            const double gi = dc ? di : 1.0;
-#pragma unroll
-            for (int q = 0; q < Q; ++q) Sacc[q] += gi * pv[q];
-        } else if (ee - es <= BIG_ROW) {
-            double A[Q], ft[Q];
-            const bool tab = dc != 0 && ee - es <= FT_D;
-            if (tab) load_vec<Q>(P->ftab + size_t(ee - es) * QMAX, ft);
-#pragma unroll
-            for (int q = 0; q < Q; ++q) A[q] = 1.0;
-            for (int e = es; e < ee; ++e) {
-                double b[Q];
-                load_vec<Q>(&sb[e * Q], b);
-#pragma unroll
-                for (int q = 0; q < Q; ++q) A[q] *= b[q];
-                rescale_pow2<Q>(A);
-            }
-            finish_row(r, di, A, nullptr, tab ? ft : nullptr);
-        }
-    }
-    if (sbig)  // uniform: written before the barrier that ends phase 1
-    for (int r = tid >> 6; r < nrows; r += frame_cfg<Q>::WAVES) {  // wave-uniform row index
-        const int es = int(srp[r]), ee = int(srp[r + 1]);
-        if (ee - es > BIG_ROW && !sfl[r]) {
-            double A[Q];
-            int ae[Q];
-            row_product_wave<Q>(sb, es, ee, A, ae);
-            if ((tid & 63) == 0) finish_row(r, double(ee - es), A, ae);
-        }
-    }
-    __syncthreads();
-
-    // ---- phase 3: lane per directed edge: cavity, normalise, damp, store
-    double *__restrict__ Mnew = Mall + (size_t(mc ^ 1) * R + rep) * msg_stride;
-    double md = 0.0;
-    const int probe2 = P->ar_probe2;  // the probe sweep of the adaptive relaxation: |m^{t+1} - m^{t-1}| (m^{t-1} sits in the slot written below)
-    damp *= P->damp_auto;
-#pragma unroll
-    for (int x = 0; x < EPT; ++x) {
-        const int le = x * frame_cfg<Q>::TPB + tid;
-        if (le < ne) {
-            const int r = srow[le];
-            double out[Q];
-            if (sfl[r]) {
-#pragma unroll
-                for (int q = 0; q < Q; ++q) out[q] = mo[x][q];
-            } else {
-                double A[Q], b[Q], cav[Q];
-                load_vec<Q>(&sA[r * Q], A);
-                load_vec<Q>(&sb[le * Q], b);
-                bool ok = true;
-                double tot = 0.0;
-#pragma unroll
-                for (int q = 0; q < Q; ++q) {
-                    cav[q] = A[q] / b[q];
-                    ok = ok && (b[q] > 0.0) && (cav[q] <= 1.7e308);
-                    tot += cav[q];
-                }
-                if (!ok) {  // exact cavity product when a division is unusable (b == 0 or overflow)
-                    const int es = int(srp[r]), ee = int(srp[r + 1]);
-                    const double di = double(ee - es);
-                    int ce[Q];
-#pragma unroll
-                    for (int q = 0; q < Q; ++q) { cav[q] = 1.0; ce[q] = 0; }
-                    for (int e = es; e < ee; ++e) {
-                        if (e == le) continue;
-#pragma unroll
-                        for (int q = 0; q < Q; ++q) cav[q] *= sb[e * Q + q];
-                        x_norm<Q>(cav, ce);
-                    }
-                    tot = apply_field_x<Q>(P, dc, di, cav, ce);
-                }
-                const double inv = 1.0 / tot;
-                double ref[Q];
-                if (probe2) {  // uniform
-                    load_msg<Q>(Mnew, size_t(e0 + le), ref);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < Q; ++q) ref[q] = mo[x][q];
-                }
-#pragma unroll
-                for (int q = 0; q < Q; ++q) {
-                    const double nv = cav[q] * inv;
-                    out[q] = damp * nv + (1.0 - damp) * mo[x][q];
-                    md = nanmax(md, probe2 ? fabs(ref[q] - out[q]) / damp : fabs(ref[q] - nv));
-                }
-            }
-            store_msg_stream<Q>(Mnew, size_t(e0 + le), out);
-        }
-    }
-    block_reduce_store<Q, frame_cfg<Q>::WAVES>(Sacc, md, sred, rec_all + size_t(rep) * rec_stride + size_t(blockIdx.x) * (Q + 1));
+#define SWEEP_MNEW double *__restrict__ Mnew = Mall + (size_t(mc ^ 1) * R + rep) * msg_stride;
+#define SWEEP_RECORD rec_all + size_t(rep) * rec_stride + size_t(blockIdx.x) * (Q + 1)
+#include "sweep_msg_body.inc"
+#undef SWEEP_REPLICA
+#undef SWEEP_MOLD
+#undef SWEEP_PSI
+#undef SWEEP_MNEW
+#undef SWEEP_RECORD
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -284,13 +118,7 @@ k_psi_sum_batch(const uint32_t *__restrict__ row_ptr, const double *__restrict__
     for (int q = 0; q < Q; ++q) S[q] = 0.0;
     const uint32_t lo = blockIdx.x * rows_per_blk;
     const uint32_t hi = min(n_rows, lo + rows_per_blk);
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += BLOCK) {
-        double pv[Q];
-        load_vec<Q>(psi + size_t(i) * Q, pv);
-        const double gi = dc ? double(row_ptr[i + 1] - row_ptr[i]) : 1.0;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) S[q] += gi * pv[q];
-    }
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += BLOCK) psi_row_add<Q>(row_ptr, psi, i, dc, S);
     block_reduce_store<Q>(S, 0.0, sred, partials + (size_t(rep) * gridDim.x + blockIdx.x) * (Q + 1));
 }
 // workgroup r: fold of replica r's chunks in a fixed order, then the exact field of P[r] (finalize_update mode 2)
@@ -338,28 +166,6 @@ __host__ __device__ constexpr int em_np(int Q) { return EM_NA + 2 * Q + Q * (Q +
 // tools/kernel_resources.py); above it k_em_edges_batch computes them
 constexpr int EM_FRAME_QMAX = 8;
 
-// per directed edge: EM numerators of k_em_edges
-template <int Q, bool DC2>
-__device__ __forceinline__ void em_edge_terms(const dev_params *__restrict__ P, const double (&mi)[Q], const double (&mo)[Q], double didl,
-                                              double (&acc)[Q * (Q + 1) / 2]) {
-    constexpr int T = Q * (Q + 1) / 2;
-    double term[T], norm_L = 0.0;
-    int t = 0;
-#pragma unroll
-    for (int q1 = 0; q1 < Q; ++q1) {
-#pragma unroll
-        for (int q2 = q1; q2 < Q; ++q2, ++t) {
-            double w = P->cab[q1 * Q + q2];
-            if (DC2) { double x = didl * w * P->invN; w = x / (1.0 + x); }
-            const double pr = (q1 == q2) ? (mi[q1] * mo[q2]) : (mi[q1] * mo[q2] + mi[q2] * mo[q1]);
-            term[t] = w * pr;
-            norm_L += term[t];
-        }
-    }
-    const double inv = 0.5 / norm_L;
-#pragma unroll
-    for (int u = 0; u < T; ++u) acc[u] += term[u] * inv;
-}
 // per directed edge (i, l): adjacent-pair term of the non-edge sum. adj_mode 1: series form (k_nonedge_adj, mat = N (1 -
 // (1 - cab/N)^beta)); 2: exact form (k_nonedge_exact_adj, mat = (1 - cab/N)^beta)
 template <int Q>
@@ -561,55 +367,8 @@ k_moments_batch(const double *__restrict__ psi_all, const int *__restrict__ par_
                 uint32_t R, uint32_t n_rows, int Q, int K, uint32_t rows_per_blk, int T, double *__restrict__ partials) {
     const uint32_t rep = blockIdx.y;
     if (!active[rep]) return;
-    __shared__ double sp[BLOCK * QMAX];
-    __shared__ double scomb[BLOCK];
-    const double *__restrict__ psi = psi_all + (size_t(par_all[rep]) * R + rep) * psi_stride;
-    double *__restrict__ out = partials + (size_t(rep) * gridDim.x + blockIdx.x) * T;
-    const int tid = threadIdx.x;
-    constexpr int MAXE = 20;  // entries per thread (k_moments)
-    double acc[MAXE];
-    for (int j = 0; j < MAXE; ++j) acc[j] = 0.0;
-    const int nsub = T < BLOCK / 2 ? BLOCK / T : 1;
-    const int sub = nsub > 1 ? tid / T : 0;
-    const bool own = nsub == 1 || tid < nsub * T;
-    const uint32_t lo = blockIdx.x * rows_per_blk, hi = min(n_rows, lo + rows_per_blk);
-    for (uint32_t base = lo; base < hi; base += BLOCK) {
-        const uint32_t cnt = min(uint32_t(BLOCK), hi - base);
-        __syncthreads();
-        for (uint32_t x = tid; x < cnt * Q; x += BLOCK) sp[x] = psi[size_t(base) * Q + x];
-        __syncthreads();
-        int j = 0;
-        for (int ent = nsub > 1 ? tid % T : tid; own && ent < T; ent += BLOCK, ++j) {
-            int k = 1, off = 0, sz = Q;
-            while (ent >= off + sz) { off += sz; sz *= Q; ++k; }
-            int idx = ent - off;
-            int a[4];
-            for (int t = 0; t < 4; ++t) { a[t] = idx % Q; idx /= Q; }
-            double s = 0.0;
-            for (uint32_t r = uint32_t(sub); r < cnt; r += uint32_t(nsub)) {
-                const double *p = &sp[r * Q];
-                double v = p[a[0]];
-                if (k > 1) v *= p[a[1]];
-                if (k > 2) v *= p[a[2]];
-                if (k > 3) v *= p[a[3]];
-                s += v;
-            }
-            acc[j] += s;
-        }
-    }
-    if (nsub > 1) {  // combine the sub-sums of an entry in a fixed order
-        __syncthreads();
-        scomb[tid] = own ? acc[0] : 0.0;
-        __syncthreads();
-        if (tid < T) {
-            double s = scomb[tid];
-            for (int u = 1; u < nsub; ++u) s += scomb[u * T + tid];
-            out[tid] = s;
-        }
-        return;
-    }
-    int j = 0;
-    for (int ent = tid; ent < T; ent += BLOCK, ++j) out[ent] = acc[j];
+    moments_chunk(psi_all + (size_t(par_all[rep]) * R + rep) * psi_stride, n_rows, Q, rows_per_blk, T,
+                  partials + (size_t(rep) * gridDim.x + blockIdx.x) * T);
 }
 
 // K4x with the replica as blockIdx.z: log(psi_i^T P_r psi_l) over all ordered pairs of replica r (k_nonedge_exact without
@@ -630,24 +389,8 @@ k_nonedge_exact_batch(const double *__restrict__ psi_all, const int *__restrict_
     const uint32_t cnt = min(uint32_t(BLOCK), n - l0);
     for (uint32_t x = threadIdx.x; x < cnt * Q; x += BLOCK) sl[x] = psi[size_t(l0) * Q + x];
     __syncthreads();
-    double acc[1] = {0.0};
-    if (i < n) {
-        double pi[Q], v[Q];
-        load_vec<Q>(psi + size_t(i) * Q, pi);
-#pragma unroll
-        for (int q2 = 0; q2 < Q; ++q2) {
-            double a = 0.0;
-#pragma unroll
-            for (int q1 = 0; q1 < Q; ++q1) a += Pmat[q1 * Q + q2] * pi[q1];
-            v[q2] = a;
-        }
-        for (uint32_t r = 0; r < cnt; ++r) {
-            double f = 0.0;
-#pragma unroll
-            for (int q = 0; q < Q; ++q) f += v[q] * sl[r * Q + q];
-            if (f != 0.0) acc[0] += log(f);
-        }
-    }
+    double acc[1] = {0.0}, no_entropy = 0.0;
+    if (i < n) nonedge_pair_sums<Q>(psi, i, sl, cnt, Pmat, nullptr, 0.0, 0, acc[0], no_entropy);
     block_sum_store<1, 4>(acc, sred, partials + size_t(rep) * gridDim.x * gridDim.y + size_t(blockIdx.y) * gridDim.x + blockIdx.x);
 }
 
