@@ -25,6 +25,7 @@
 #include "../../include/sbmbp.h"
 #include "host_graph.h"
 #include "host_loops.h"
+#include "host_reduce.h"
 
 using sbmbp::set_error;
 using sbmbp::arg_error;
@@ -907,7 +908,7 @@ int fe_terms(sbmbp_dist *d, bool want_entropy, double out[6]) {
     CHK(sbmbp_shard_fe_finish(d->eng, fe));
     double ne[2] = {0.0, 0.0};
     const u32 N = d->plan.n_global;
-    if (d->dc == 0 && N <= 32768) {
+    if (d->dc == 0 && sbmbp::nonedge_is_exact(0, N)) {
         // small graphs: the reference's O(N^2) loop exactly, as the single engine does: every rank gets the marginals of all
         // vertices (own rows summed into a global table) and sums its own rows against them
         if (!d->d_psi_all) CHK(dalloc(&d->d_psi_all, size_t(N) * d->Q));
@@ -919,8 +920,7 @@ int fe_terms(sbmbp_dist *d, bool want_entropy, double out[6]) {
         CHK(reduce_red(d, 4, 0));
         double v[4];
         CHK(read_red(d, v, 4));
-        ne[0] = (v[0] - v[2]) / (2.0 * N);
-        ne[1] = (v[1] - v[3]) / (2.0 * N);
+        sbmbp::nonedge_finish(v, v + 2, N, ne);
     } else {
         u32 n = 0;
         int order = 0;
@@ -948,19 +948,7 @@ int overlap_of(sbmbp_dist *d, double *ov, double *Cout) {
     CHK(row_sums(d, rs));
     const double *C = rs.data() + 2 * Q;
     if (Cout) std::copy(C, C + Q * Q, Cout);
-    if (ov) {
-        std::vector<u32> perm(Q);
-        std::iota(perm.begin(), perm.end(), 0u);
-        double best = -1.0;
-        do {  // compute_overlap (bp.cpp:775-811): all Q! permutations for Q <= 8, the identity alone above (:784-790)
-            double s = 0.0;
-            for (u32 a = 0; a < Q; ++a) s += C[a * Q + perm[a]];
-            s /= double(d->plan.n_global);
-            if (s > best) best = s;
-            if (Q > 8) break;
-        } while (std::next_permutation(perm.begin(), perm.end()));
-        *ov = best;
-    }
+    if (ov) *ov = sbmbp::best_overlap(Q, d->plan.n_global, C);
     return SBMBP_OK;
 }
 
@@ -1291,8 +1279,8 @@ int sbmbp_dist_free_energy(sbmbp_dist_t *d, double *f, double *parts) {
     device_guard guard(d->device);
     double t[6];
     CHK(fe_terms(d, false, t));
-    if (parts) { parts[0] = t[0]; parts[1] = t[1]; parts[2] = t[2]; }
-    if (f) *f = -t[0] + t[1] + t[2];
+    if (parts) std::copy(t, t + 3, parts);
+    if (f) *f = sbmbp::free_energy_of(t);
     return SBMBP_OK;
 }
 
@@ -1307,8 +1295,8 @@ int sbmbp_dist_entropy(sbmbp_dist_t *d, double *ent, double *parts) {
     }
     double t[6];
     CHK(fe_terms(d, true, t));
-    if (parts) { parts[0] = t[3]; parts[1] = t[4]; parts[2] = t[5]; }
-    if (ent) *ent = -t[3] + t[4] - t[5];
+    if (parts) std::copy(t + 3, t + 6, parts);
+    if (ent) *ent = sbmbp::entropy_of(t + 3);
     return SBMBP_OK;
 }
 
@@ -1337,8 +1325,8 @@ int sbmbp_dist_inference(sbmbp_dist_t *d, float conv_crit, uint32_t time_conv, f
     CHK(run(d, double(conv_crit), time_conv, double(dumping_rate), &out->niter, &out->last_maxdiff));
     double t[6];
     CHK(fe_terms(d, d->dc == 0, t));
-    out->free_energy = -t[0] + t[1] + t[2];
-    out->entropy = d->dc == 0 ? -t[3] + t[4] - t[5] : std::nan("");
+    out->free_energy = sbmbp::free_energy_of(t);
+    out->entropy = d->dc == 0 ? sbmbp::entropy_of(t + 3) : std::nan("");
     return overlap_of(d, &out->overlap, nullptr);
 }
 
@@ -1364,7 +1352,7 @@ int sbmbp_dist_learning(sbmbp_dist_t *d, float learning_conv_crit, uint32_t lear
             CHK(em_expect(d, na_e, nna_e, cab_e));
             double tt[6];
             CHK(fe_terms(d, false, tt));
-            *f = -tt[0] + tt[1] + tt[2];
+            *f = sbmbp::free_energy_of(tt);
             return SBMBP_OK;
         }
         void params(u32, std::vector<u32> &na, std::vector<double> &cab) { na = d->na; cab = d->cab; }

@@ -17,6 +17,7 @@
 #include "../../include/sbmbp.h"
 #include "host_graph.h"
 #include "host_loops.h"
+#include "host_reduce.h"
 #include "kernels.h"
 #include "kernels_wide.h"
 #include "kernels_batch.h"
@@ -827,24 +828,53 @@ int refresh_field(sbmbp_engine *e) {
     return SBMBP_OK;
 }
 
-// the three Q x Q matrices of the non-edge term in d_mats: N(1 - (1-cab/N)^beta), (1-cab/N)^beta, cab   (bp.cpp:675-741)
+// the three Q x Q matrices of the non-edge term (host_reduce.h nonedge_mats, over the vertices of the whole graph) in d_mats
+// (a shard allocates it on first use)
 int upload_nonedge_mats(sbmbp_engine *e, std::vector<double> &mats, double *wmax_out) {
-    const uint32_t Q = e->Q, N = e->N;
-    mats.assign(3 * Q * Q, 0.0);
-    double *wmat = mats.data(), *Pmat = mats.data() + Q * Q, *cabm = mats.data() + 2 * Q * Q;
-    double wmax = 0.0;
-    for (uint32_t a = 0; a < Q * Q; ++a) {
-        Pmat[a] = std::pow(1.0 - e->cab[a] / double(N), e->beta);
-        wmat[a] = double(N) * (1.0 - Pmat[a]);
-        cabm[a] = e->cab[a];
-        wmax = std::max(wmax, std::max(wmat[a], cabm[a]));
-    }
+    mats.assign(3 * e->Q * e->Q, 0.0);
+    nonedge_mats(e->Q, e->Nglob, e->cab.data(), e->beta, mats.data(), wmax_out);
+    if (!e->d_mats) CHK(dev_alloc(e, &e->d_mats, mats.size()));
     HIPCHK(hipMemcpyAsync(e->d_mats, mats.data(), mats.size() * 8, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (wmax_out) *wmax_out = wmax;
     return SBMBP_OK;
 }
-inline bool nonedge_exact(const sbmbp_engine *e) { return (e->nonedge_mode == 1) || (e->nonedge_mode == 0 && e->N <= 32768); }
+inline bool nonedge_exact(const sbmbp_engine *e) { return nonedge_is_exact(e->nonedge_mode, e->N); }
+
+// copy of n folded doubles to the host; returns when they have arrived
+int read_doubles(sbmbp_engine *e, const double *d_src, size_t n, double *out) {
+    HIPCHK(hipMemcpyAsync(out, d_src, n * 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return SBMBP_OK;
+}
+
+// moment tensors of orders 1 .. K of this engine's rows (T = series_len(Q, K) doubles), folded into d_out
+int moments_to_device(sbmbp_engine *e, int K, uint32_t T, double *d_out) {
+    const uint32_t rows_per_blk = 512;  // one thread per output entry loops over staged rows: keep chunks small, workgroups many
+    const uint32_t nb = std::max<uint32_t>(1, (e->N + rows_per_blk - 1) / rows_per_blk);
+    CHK(ensure_partials(e, size_t(nb) * T));
+    hipLaunchKernelGGL(k_moments, dim3(nb), dim3(BLOCK), 0, e->stream, e->d_psi[e->pcur], e->N, int(e->Q), K, rows_per_blk, int(T), e->d_partials);
+    HIPCHK(hipGetLastError());
+    return fold_matrix_to_device(e, nb, T, d_out);
+}
+
+// adjacent pairs of the non-edge term over this engine's rows, folded into d_out[0 .. NE_NP): in the form of the exact loop
+// (P = d_mats + Q Q) or of the series (w = d_mats)
+int adjacent_pairs_to_device(sbmbp_engine *e, bool exact, bool want_entropy, double *d_out) {
+    const uint32_t Q = e->Q;
+    const double invN = 1.0 / double(e->Nglob);
+    const double *d_cab = e->d_mats + 2 * Q * Q;
+    CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (NE_NP + 1)));
+    if (exact) {
+        DISPATCH_Q(Q, hipLaunchKernelGGL((k_nonedge_exact_adj<QQ>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
+                                         e->d_nbr, e->d_psi[e->pcur], e->d_mats + Q * Q, d_cab, e->d_blk_row, invN, int(want_entropy),
+                                         e->d_partials));
+    } else {
+        DISPATCH_Q(Q, hipLaunchKernelGGL((k_nonedge_adj<QQ>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
+                                         e->d_nbr, e->d_psi[e->pcur], e->d_mats, d_cab, e->d_blk_row, invN, int(want_entropy), e->d_partials));
+    }
+    HIPCHK(hipGetLastError());
+    return fold_to_device(e, e->n_blk, NE_NP, NE_NP + 1, d_out);
+}
 
 // May the reductions take the fused pass on the marginal-gather reconstruction (k_fe_psi)? It needs exactly what the
 // marginal-gather SWEEP needs, and psi must be the marginals of the message pair in d_M: the state a converge call leaves.
@@ -953,61 +983,6 @@ int site_edge_terms(sbmbp_engine *e, bool want_entropy, double out[4], double *d
     return fold_to_host(e, e->n_blk, FE_NP, FE_NP + 1, out);
 }
 
-// contraction <M_k, (m_0 x ... x m_{k-1}) M_k> of SURVEY A.4 on the host: the matrices are applied one tensor mode after the
-// other (k Q^(k+1) multiplications; summing all Q^2k terms directly took 0.1 s per call at Q = 64, k = 2 or Q = 16, k = 3 -
-// ten times the device side of the whole reduction pass). Mode j is digit j of the index, the least significant first.
-double contract(const double *Mk, uint32_t Q, unsigned k, const std::vector<const double *> &mats) {
-    size_t T = 1;
-    for (unsigned j = 0; j < k; ++j) T *= Q;
-    std::vector<double> cur(Mk, Mk + T), nxt(T);
-    size_t stride = 1;
-    for (unsigned j = 0; j < k; ++j) {
-        const double *m = mats[j];
-        const size_t outer = T / (stride * Q);
-        for (size_t hi = 0; hi < outer; ++hi)
-            for (uint32_t a = 0; a < Q; ++a) {
-                double *dst = nxt.data() + (hi * Q + a) * stride;
-                for (size_t lo = 0; lo < stride; ++lo) dst[lo] = 0.0;
-                for (uint32_t b = 0; b < Q; ++b) {
-                    const double w = m[a * Q + b];
-                    const double *src = cur.data() + (hi * Q + b) * stride;
-                    for (size_t lo = 0; lo < stride; ++lo) dst[lo] += w * src[lo];
-                }
-            }
-        cur.swap(nxt);
-        stride *= Q;
-    }
-    double acc = 0.0;
-    for (size_t a = 0; a < T; ++a) acc += Mk[a] * cur[a];
-    return acc;
-}
-
-// highest series order whose moment tensors (Q + Q^2 + ... + Q^K doubles) fit k_moments (20 entries per thread of a
-// 256-thread workgroup = 5120) and the reduction buffers: 4 up to Q = 8, 3 above
-int max_series_order(uint32_t Q) {
-    int K = 0;
-    uint64_t T = 0, sz = 1;
-    while (K < 4) {
-        sz *= Q;
-        if (T + sz > 5120) break;
-        T += sz;
-        ++K;
-    }
-    return K;
-}
-
-int choose_series_order(const sbmbp_engine *e, double wmax) {
-    const int Kmax = max_series_order(e->Q);
-    if (e->series_order > 0) return std::min(e->series_order, Kmax);
-    // smallest K with N (wmax/N)^(K+1) / (2(K+1)) < 1e-12  (SURVEY A.4 truncation bound); where no K up to the cap meets it,
-    // the cap - silently, and then the bound of the cap is what holds (1e-7 at Q = 32, N = 4e4, c = 10)
-    for (int K = 1; K <= Kmax; ++K) {
-        double err = double(e->N) * std::pow(wmax / double(e->N), K + 1) / (2.0 * (K + 1));
-        if (err < 1e-12) return K;
-    }
-    return Kmax;
-}
-
 // non-edge terms: out[0] = f_nonedge, out[1] = e_nonedge (if want_entropy)   (bp.cpp:675-741)
 int nonedge_terms(sbmbp_engine *e, bool want_entropy, double out[2]) {
     out[0] = out[1] = 0.0;
@@ -1017,8 +992,7 @@ int nonedge_terms(sbmbp_engine *e, bool want_entropy, double out[2]) {
     std::vector<double> mats;
     double wmax = 0.0;
     CHK(upload_nonedge_mats(e, mats, &wmax));
-    const double *wmat = mats.data(), *cabm = mats.data() + 2 * Q * Q;
-    const double *d_w = e->d_mats, *d_Pm = e->d_mats + Q * Q, *d_cab = e->d_mats + 2 * Q * Q;
+    const double *d_Pm = e->d_mats + Q * Q, *d_cab = e->d_mats + 2 * Q * Q;
     const bool exact = nonedge_exact(e);
     double adj[2] = {0.0, 0.0}, all[2] = {0.0, 0.0};
     const bool adj_known = use_fz(e) && e->fz.valid && (e->fz.entropy || !want_entropy);  // the fused pass has the adjacent pairs already
@@ -1040,56 +1014,21 @@ int nonedge_terms(sbmbp_engine *e, bool want_entropy, double out[2]) {
         HIPCHK(hipGetLastError());
         CHK(fold_to_host(e, g * g, NE_NP, NE_NP + 1, all));
         }
-        if (!adj_known) {
-        CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (NE_NP + 1)));
-        DISPATCH_Q(Q, hipLaunchKernelGGL((k_nonedge_exact_adj<QQ>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
-                                         e->d_nbr, e->d_psi[e->pcur], d_Pm, d_cab, e->d_blk_row, invN, int(want_entropy),
-                                         e->d_partials));
-        HIPCHK(hipGetLastError());
-        CHK(fold_to_host(e, e->n_blk, NE_NP, NE_NP + 1, adj));
-        }
     } else {
-        const int K = choose_series_order(e, wmax);
-        const int Kent = want_entropy ? K : 0;  // entropy term k uses M_{k+1}: orders 1..K as well
-        (void)Kent;
-        int T = 0, sz = 1;
-        for (int k = 1; k <= K; ++k) { sz *= int(Q); T += sz; }
-        const uint32_t rows_per_blk = 512;  // one thread per output entry loops over staged rows: keep chunks small, workgroups many
-        const uint32_t nb = std::max<uint32_t>(1, (N + rows_per_blk - 1) / rows_per_blk);
-        CHK(ensure_partials(e, size_t(nb) * T));
-        CHK(ensure_small(e, size_t(T)));
-        hipLaunchKernelGGL(k_moments, dim3(nb), dim3(BLOCK), 0, e->stream, e->d_psi[e->pcur], N, int(Q), K, rows_per_blk, T, e->d_partials);
-        HIPCHK(hipGetLastError());
-        CHK(fold_matrix_to_device(e, nb, uint32_t(T), e->d_small));
+        const int K = series_order(Q, N, e->series_order, wmax);
+        const uint32_t T = series_len(Q, K);
+        CHK(ensure_small(e, T));
+        CHK(moments_to_device(e, K, T, e->d_small));
         std::vector<double> Mk(T);
-        HIPCHK(hipMemcpyAsync(Mk.data(), e->d_small, size_t(T) * 8, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        std::vector<double> vmat(Q * Q);
-        for (uint32_t a = 0; a < Q * Q; ++a) vmat[a] = cabm[a] * std::log(cabm[a]);
-        double Nk = 1.0;
-        size_t off = 0, tsz = 1;
-        for (int k = 1; k <= K; ++k) {
-            tsz *= Q;
-            Nk *= double(N);
-            std::vector<const double *> ms(k, wmat);
-            all[0] -= contract(Mk.data() + off, Q, unsigned(k), ms) / (double(k) * Nk);
-            if (want_entropy) {  // term (k-1): (u/N)(y/N)^(k-1) -> <M_k, (v x cab^(k-1)) M_k> / N^k
-                std::vector<const double *> me(k, cabm);
-                me[0] = vmat.data();
-                all[1] += contract(Mk.data() + off, Q, unsigned(k), me) / Nk;
-            }
-            off += tsz;
-        }
-        if (!adj_known) {
-        CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (NE_NP + 1)));
-        DISPATCH_Q(Q, hipLaunchKernelGGL((k_nonedge_adj<QQ>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
-                                         e->d_nbr, e->d_psi[e->pcur], d_w, d_cab, e->d_blk_row, invN, int(want_entropy), e->d_partials));
-        HIPCHK(hipGetLastError());
-        CHK(fold_to_host(e, e->n_blk, NE_NP, NE_NP + 1, adj));
-        }
+        CHK(read_doubles(e, e->d_small, T, Mk.data()));
+        nonedge_series(Q, N, K, want_entropy, Mk.data(), mats.data(), all);
     }
-    out[0] = (all[0] - adj[0]) / (2.0 * N);
-    out[1] = (all[1] - adj[1]) / (2.0 * N);
+    if (!adj_known) {
+        CHK(ensure_small(e, NE_NP));
+        CHK(adjacent_pairs_to_device(e, exact, want_entropy, e->d_small));
+        CHK(read_doubles(e, e->d_small, NE_NP, adj));
+    }
+    nonedge_finish(all, adj, N, out);
     return SBMBP_OK;
 }
 
@@ -1114,7 +1053,6 @@ int row_sums(sbmbp_engine *e, std::vector<double> &out /* 2Q + Q*Q */) {
     return SBMBP_OK;
 }
 
-void em_rescale(uint32_t Q, uint32_t N, uint32_t dc, const double *na, const double *nna, const double *tri, double *ce);
 int em_expect(sbmbp_engine *e, double *na_e, double *nna_e, double *cab_e) {
     if (!e->have_params || !e->have_state) { set_error("engine has no parameters or no state"); return SBMBP_ERR_STATE; }
     const uint32_t Q = e->Q;
@@ -1175,12 +1113,11 @@ int free_energy_impl(sbmbp_engine *e, double *f, double *parts) {
     double se[4], ne[2];
     CHK(site_edge_terms(e, false, se));
     CHK(nonedge_terms(e, false, ne));
-    const double N = double(e->N);
-    double f_site = se[0] / N, f_edge = se[1] / (2.0 * N);
-    if (e->dc == 1) { f_site += e->sum_log_didl / N; f_edge += e->sum_log_didl / (2.0 * N); }  // SURVEY A.3 dc-1 note
-    const double f_non = ne[0];
-    if (parts) { parts[0] = f_site; parts[1] = f_edge; parts[2] = f_non; }
-    if (f) *f = -f_site + f_edge + f_non;
+    double p[4];
+    site_edge_parts(e->N, e->dc == 1 ? &e->sum_log_didl : nullptr, se, p);
+    const double fp[3] = {p[0], p[1], ne[0]};
+    if (parts) std::copy(fp, fp + 3, parts);
+    if (f) *f = free_energy_of(fp);
     return SBMBP_OK;
 }
 
@@ -1195,10 +1132,11 @@ int entropy_impl(sbmbp_engine *e, double *ent, double *parts) {
     double se[4], ne[2];
     CHK(site_edge_terms(e, true, se));
     CHK(nonedge_terms(e, true, ne));
-    const double N = double(e->N);
-    const double e_site = se[2] / N, e_edge = se[3] / (2.0 * N), e_non = ne[1];
-    if (parts) { parts[0] = e_site; parts[1] = e_edge; parts[2] = e_non; }
-    if (ent) *ent = -e_site + e_edge - e_non;
+    double p[4];
+    site_edge_parts(e->N, nullptr, se, p);
+    const double ep[3] = {p[2], p[3], ne[1]};
+    if (parts) std::copy(ep, ep + 3, parts);
+    if (ent) *ent = entropy_of(ep);
     return SBMBP_OK;
 }
 
@@ -1209,50 +1147,8 @@ int overlap_impl(sbmbp_engine *e, double *ov, double *Cout) {
     CHK(row_sums(e, rs));
     const double *C = rs.data() + 2 * Q;
     if (Cout) std::copy(C, C + Q * Q, Cout);
-    if (ov) {
-        std::vector<uint32_t> perm(Q);
-        std::iota(perm.begin(), perm.end(), 0u);
-        double best = -1.0;
-        do {  // compute_overlap (bp.cpp:775-811): all Q! permutations for Q <= 8, the identity alone above (:784-790)
-            double s = 0.0;
-            for (uint32_t a = 0; a < Q; ++a) s += C[a * Q + perm[a]];
-            s /= double(e->N);
-            if (s > best) best = s;
-            if (Q > 8) break;
-        } while (std::next_permutation(perm.begin(), perm.end()));
-        *ov = best;
-    }
+    if (ov) *ov = best_overlap(Q, e->N, C);
     return SBMBP_OK;
-}
-
-// which of n runs is best (sbmbp.h: sbmbp_best_replica)
-uint32_t best_replica(uint32_t n, const double *f, const int *rank, int n_ranks) {
-    int pick = -1;
-    for (int pass = 0; pass < n_ranks && pick < 0; ++pass)
-        for (uint32_t r = 0; r < n; ++r) {
-            if (rank[r] != pass || std::isnan(f[r])) continue;
-            if (pick < 0 || f[r] < f[pick]) pick = int(r);
-        }
-    return pick < 0 ? 0u : uint32_t(pick);
-}
-
-// cab_expect from the Q (Q + 1) / 2 numerators: symmetric fill and the rescaling of belief_propagation.cpp:967-988
-void em_rescale(uint32_t Q, uint32_t N, uint32_t dc, const double *na, const double *nna, const double *tri, double *ce) {
-    uint32_t t = 0;
-    for (uint32_t q1 = 0; q1 < Q; ++q1)
-        for (uint32_t q2 = q1; q2 < Q; ++q2, ++t) { ce[q1 * Q + q2] = tri[t]; ce[q2 * Q + q1] = tri[t]; }
-    const double EPS = 1.0e-50;
-    const double *nn = (dc == 0) ? na : nna;
-    for (uint32_t q1 = 0; q1 < Q; ++q1)
-        for (uint32_t q2 = q1; q2 < Q; ++q2)
-            if (na[q1] > EPS && na[q2] > EPS) {
-                if (q1 != q2) {
-                    ce[q1 * Q + q2] *= double(N) / (nn[q1] * nn[q2]);
-                    ce[q2 * Q + q1] = ce[q1 * Q + q2];
-                } else {
-                    ce[q1 * Q + q2] *= 2. * double(N) / (nn[q1] * nn[q2]);
-                }
-            }
 }
 
 void apply_params_host(sbmbp_engine *e, const double *cab, const uint32_t *na, double beta) {
@@ -1820,9 +1716,11 @@ static int inference_reductions(sbmbp_engine *e, sbmbp_infer_result *out) {
         double se[4], ne[2];
         CHK(site_edge_terms(e, true, se));
         CHK(nonedge_terms(e, true, ne));
-        const double N = double(e->N);
-        out->free_energy = -(se[0] / N) + se[1] / (2.0 * N) + ne[0];
-        out->entropy = -(se[2] / N) + se[3] / (2.0 * N) - ne[1];
+        double p[4];
+        site_edge_parts(e->N, nullptr, se, p);
+        const double fp[3] = {p[0], p[1], ne[0]}, ep[3] = {p[2], p[3], ne[1]};
+        out->free_energy = free_energy_of(fp);
+        out->entropy = entropy_of(ep);
     }
     CHK(overlap_impl(e, &out->overlap, nullptr));
     return SBMBP_OK;
@@ -2326,27 +2224,6 @@ static int shard_materialize(sbmbp_engine_t *e) {
     return SBMBP_OK;
 }
 
-static void shard_nonedge_mats(const sbmbp_engine_t *e, std::vector<double> &mats, double &wmax) {
-    const uint32_t Q = e->Q;
-    mats.assign(3 * Q * Q, 0.0);
-    wmax = 0.0;
-    for (uint32_t a = 0; a < Q * Q; ++a) {
-        const double Pm = std::pow(1.0 - e->cab[a] / double(e->Nglob), e->beta);
-        mats[a] = double(e->Nglob) * (1.0 - Pm);  // w
-        mats[Q * Q + a] = Pm;
-        mats[2 * Q * Q + a] = e->cab[a];
-        wmax = std::max(wmax, std::max(mats[a], e->cab[a]));
-    }
-}
-
-static int shard_series_order(const sbmbp_engine_t *e, double wmax) {
-    const int Kmax = max_series_order(e->Q);
-    if (e->series_order > 0) return std::min(e->series_order, Kmax);
-    for (int K = 1; K <= Kmax; ++K)
-        if (double(e->Nglob) * std::pow(wmax / double(e->Nglob), K + 1) / (2.0 * (K + 1)) < 1e-12) return K;
-    return Kmax;
-}
-
 extern "C" {
 
 // red[0..4) = {sum log Z_i, sum log norm_L, e_site sum, e_edge sum} over owned rows/edges; red[4] = sum 2 d log d
@@ -2367,14 +2244,8 @@ int sbmbp_shard_fe_finish(sbmbp_engine_t *e, double *out) {
     device_scope dev_(e);
     IS_SHARD(e);
     double r[5];
-    HIPCHK(hipMemcpyAsync(r, e->d_red, sizeof r, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    const double N = double(e->Nglob);
-    out[0] = r[0] / N;
-    out[1] = r[1] / (2.0 * N);
-    if (e->dc == 1) { out[0] += r[4] / N; out[1] += r[4] / (2.0 * N); }
-    out[2] = r[2] / N;
-    out[3] = r[3] / (2.0 * N);
+    CHK(read_doubles(e, e->d_red, 5, r));
+    site_edge_parts(e->Nglob, e->dc == 1 ? r + 4 : nullptr, r, out);
     return SBMBP_OK;
 }
 
@@ -2388,27 +2259,13 @@ int sbmbp_shard_nonedge_partial(sbmbp_engine_t *e, int want_entropy, uint32_t *n
     if (e->dc != 0) { *n_values = 0; *order = 0; return SBMBP_OK; }
     std::vector<double> mats;
     double wmax;
-    shard_nonedge_mats(e, mats, wmax);
-    const int K = shard_series_order(e, wmax);
-    int T = 0, sz = 1;
-    for (int k = 1; k <= K; ++k) { sz *= int(Q); T += sz; }
-    if (uint32_t(T) + 2 > 8192) { set_error("moment tensors do not fit the reduction buffer"); return SBMBP_ERR_UNSUPPORTED; }
-    if (!e->d_mats) CHK(dev_alloc(e, &e->d_mats, 3 * Q * Q));
-    HIPCHK(hipMemcpyAsync(e->d_mats, mats.data(), mats.size() * 8, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    const uint32_t rows_per_blk = 512;  // one thread per output entry loops over staged rows: keep chunks small, workgroups many
-    const uint32_t nb = std::max<uint32_t>(1, (e->N + rows_per_blk - 1) / rows_per_blk);
-    CHK(ensure_partials(e, size_t(nb) * T));
-    hipLaunchKernelGGL(k_moments, dim3(nb), dim3(BLOCK), 0, e->stream, e->d_psi[e->pcur], e->N, int(Q), K, rows_per_blk, T, e->d_partials);
-    HIPCHK(hipGetLastError());
-    CHK(fold_matrix_to_device(e, nb, uint32_t(T), e->d_red));
-    CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (NE_NP + 1)));
-    DISPATCH_Q(Q, hipLaunchKernelGGL((k_nonedge_adj<QQ>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_nbr,
-                                     e->d_psi[e->pcur], e->d_mats, e->d_mats + 2 * Q * Q, e->d_blk_row, 1.0 / double(e->Nglob),
-                                     want_entropy, e->d_partials));
-    HIPCHK(hipGetLastError());
-    CHK(fold_to_device(e, e->n_blk, NE_NP, NE_NP + 1, e->d_red + T));
-    *n_values = uint32_t(T) + 2;
+    CHK(upload_nonedge_mats(e, mats, &wmax));
+    const int K = series_order(Q, e->Nglob, e->series_order, wmax);
+    const uint32_t T = series_len(Q, K);
+    if (T + 2 > 8192) { set_error("moment tensors do not fit the reduction buffer"); return SBMBP_ERR_UNSUPPORTED; }
+    CHK(moments_to_device(e, K, T, e->d_red));
+    CHK(adjacent_pairs_to_device(e, false, want_entropy != 0, e->d_red + T));
+    *n_values = T + 2;
     *order = K;
     return SBMBP_OK;
 }
@@ -2424,11 +2281,7 @@ int sbmbp_shard_nonedge_exact_partial(sbmbp_engine_t *e, const double *d_psi_all
     const uint32_t Q = e->Q;
     if (e->dc != 0) { HIPCHK(hipMemsetAsync(e->d_red, 0, 4 * 8, e->stream)); return SBMBP_OK; }
     std::vector<double> mats;
-    double wmax;
-    shard_nonedge_mats(e, mats, wmax);
-    if (!e->d_mats) CHK(dev_alloc(e, &e->d_mats, 3 * Q * Q));
-    HIPCHK(hipMemcpyAsync(e->d_mats, mats.data(), mats.size() * 8, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    CHK(upload_nonedge_mats(e, mats, nullptr));
     const double *d_Pm = e->d_mats + Q * Q, *d_cab = e->d_mats + 2 * Q * Q;
     const double invN = 1.0 / double(e->Nglob);
     const uint32_t gi = (e->N + BLOCK - 1) / BLOCK, gl = (e->Nglob + BLOCK - 1) / BLOCK;
@@ -2437,12 +2290,7 @@ int sbmbp_shard_nonedge_exact_partial(sbmbp_engine_t *e, const double *d_psi_all
                                      e->Nglob, d_Pm, d_cab, invN, want_entropy, e->d_partials));
     HIPCHK(hipGetLastError());
     CHK(fold_to_device(e, gi * gl, NE_NP, NE_NP + 1, e->d_red));
-    CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (NE_NP + 1)));
-    DISPATCH_Q(Q, hipLaunchKernelGGL((k_nonedge_exact_adj<QQ>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_nbr,
-                                     e->d_psi[e->pcur], d_Pm, d_cab, e->d_blk_row, invN, want_entropy, e->d_partials));
-    HIPCHK(hipGetLastError());
-    CHK(fold_to_device(e, e->n_blk, NE_NP, NE_NP + 1, e->d_red + 2));
-    return SBMBP_OK;
+    return adjacent_pairs_to_device(e, true, want_entropy != 0, e->d_red + 2);
 }
 
 // out = {f_nonedge, e_nonedge} from the all-reduced moments and adjacent sums
@@ -2451,35 +2299,13 @@ int sbmbp_shard_nonedge_finish(sbmbp_engine_t *e, int want_entropy, int order, d
     IS_SHARD(e);
     out[0] = out[1] = 0.0;
     if (e->dc != 0 || order <= 0) return SBMBP_OK;
-    const uint32_t Q = e->Q;
-    int T = 0, sz = 1;
-    for (int k = 1; k <= order; ++k) { sz *= int(Q); T += sz; }
-    std::vector<double> r(T + 2);
-    HIPCHK(hipMemcpyAsync(r.data(), e->d_red, r.size() * 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    std::vector<double> mats;
-    double wmax;
-    shard_nonedge_mats(e, mats, wmax);
-    const double *wmat = mats.data(), *cabm = mats.data() + 2 * Q * Q;
-    std::vector<double> vmat(Q * Q);
-    for (uint32_t a = 0; a < Q * Q; ++a) vmat[a] = cabm[a] * std::log(cabm[a]);
-    const double N = double(e->Nglob);
-    double all0 = 0.0, all1 = 0.0, Nk = 1.0;
-    size_t off = 0, tsz = 1;
-    for (int k = 1; k <= order; ++k) {
-        tsz *= Q;
-        Nk *= N;
-        std::vector<const double *> ms(k, wmat);
-        all0 -= contract(r.data() + off, Q, unsigned(k), ms) / (double(k) * Nk);
-        if (want_entropy) {
-            std::vector<const double *> me(k, cabm);
-            me[0] = vmat.data();
-            all1 += contract(r.data() + off, Q, unsigned(k), me) / Nk;
-        }
-        off += tsz;
-    }
-    out[0] = (all0 - r[T]) / (2.0 * N);
-    out[1] = (all1 - r[T + 1]) / (2.0 * N);
+    const uint32_t Q = e->Q, T = series_len(Q, order);
+    std::vector<double> r(T + 2), mats(3 * Q * Q);
+    CHK(read_doubles(e, e->d_red, r.size(), r.data()));
+    nonedge_mats(Q, e->Nglob, e->cab.data(), e->beta, mats.data(), nullptr);
+    double all[2];
+    nonedge_series(Q, e->Nglob, order, want_entropy != 0, r.data(), mats.data(), all);
+    nonedge_finish(all, r.data() + T, e->Nglob, out);
     return SBMBP_OK;
 }
 
@@ -2512,21 +2338,10 @@ int sbmbp_shard_em_finish(sbmbp_engine_t *e, double *na_e, double *nna_e, double
     IS_SHARD(e);
     const uint32_t Q = e->Q, R = 2 * Q + Q * Q, T = Q * (Q + 1) / 2;
     std::vector<double> r(R + T);
-    HIPCHK(hipMemcpyAsync(r.data(), e->d_red, r.size() * 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    CHK(read_doubles(e, e->d_red, r.size(), r.data()));
     const double *na = r.data(), *nna = r.data() + Q, *tri = r.data() + R;
     std::vector<double> ce(Q * Q, 0.0);
-    uint32_t t = 0;
-    for (uint32_t q1 = 0; q1 < Q; ++q1)
-        for (uint32_t q2 = q1; q2 < Q; ++q2, ++t) { ce[q1 * Q + q2] = tri[t]; ce[q2 * Q + q1] = tri[t]; }
-    const double EPS = 1.0e-50;  // rescaling of belief_propagation.cpp:967-988
-    const double *nn = (e->dc == 0) ? na : nna;
-    for (uint32_t q1 = 0; q1 < Q; ++q1)
-        for (uint32_t q2 = q1; q2 < Q; ++q2)
-            if (na[q1] > EPS && na[q2] > EPS) {
-                if (q1 != q2) { ce[q1 * Q + q2] *= double(e->Nglob) / (nn[q1] * nn[q2]); ce[q2 * Q + q1] = ce[q1 * Q + q2]; }
-                else ce[q1 * Q + q2] *= 2. * double(e->Nglob) / (nn[q1] * nn[q2]);
-            }
+    em_rescale(Q, e->Nglob, e->dc, na, nna, tri, ce.data());
     if (na_e) std::copy(na, na + Q, na_e);
     if (nna_e) std::copy(nna, nna + Q, nna_e);
     if (cab_e) std::copy(ce.begin(), ce.end(), cab_e);
@@ -2789,19 +2604,13 @@ int batch_reductions(sbmbp_batch *b, const uint8_t *mask, double *na_e, double *
         h_ref[r] = (on && !p.field_fresh) ? 1 : 0;
         any = any || on;
         any_refresh = any_refresh || h_ref[r];
-        double *wmat = h_mats + size_t(r) * 3 * QQ2, *Pmat = wmat + QQ2, *cabm = wmat + 2 * QQ2;
-        double wmax = 0.0;
-        for (uint32_t a = 0; a < QQ2; ++a) {  // (upload_nonedge_mats)
-            Pmat[a] = on ? std::pow(1.0 - p.cab[a] / double(N), p.beta) : 0.0;
-            wmat[a] = double(N) * (1.0 - Pmat[a]);
-            cabm[a] = on ? p.cab[a] : 0.0;
-            wmax = std::max(wmax, std::max(wmat[a], cabm[a]));
-        }
-        if (on && nonedge && !exact) { Kr[r] = choose_series_order(e, wmax); K = std::max(K, Kr[r]); }
+        double *wmat = h_mats + size_t(r) * 3 * QQ2, wmax = 0.0;
+        if (on) nonedge_mats(Q, N, p.cab.data(), p.beta, wmat, &wmax);
+        else for (uint32_t a = 0; a < 3 * QQ2; ++a) wmat[a] = a < QQ2 ? double(N) : 0.0;  // the matrices of P = cab = 0: never read, but uploaded
+        if (on && nonedge && !exact) { Kr[r] = series_order(Q, N, e->series_order, wmax); K = std::max(K, Kr[r]); }
     }
     if (!any) return SBMBP_OK;
-    uint32_t Tm = 0;
-    { uint32_t sz = 1; for (int k = 1; k <= K; ++k) { sz *= Q; Tm += sz; } }
+    const uint32_t Tm = series_len(Q, K);
     const uint32_t n_all = nonedge ? (exact ? 1u : Tm) : 0u, RES = NP + n_all;
 
     // ---- buffers
@@ -2882,7 +2691,6 @@ int batch_reductions(sbmbp_batch *b, const uint8_t *mask, double *na_e, double *
 
     // ---- host: per replica
     const double *res = static_cast<const double *>(b->h_em_res);
-    const double Nd = double(N);
     std::vector<double> ce(QQ2);
     for (uint32_t r = 0; r < R; ++r) {
         if (!h_act[r]) continue;
@@ -2895,29 +2703,18 @@ int batch_reductions(sbmbp_batch *b, const uint8_t *mask, double *na_e, double *
             em_rescale(Q, N, e->dc, na, nna, tri, ce.data());
             std::copy(ce.begin(), ce.end(), cab_e + size_t(r) * QQ2);
         }
-        if (f || parts) {  // (free_energy_impl, nonedge_terms)
-            double f_site = row[0] / Nd, f_edge = row[1] / (2.0 * Nd), f_non = 0.0;
-            if (e->dc == 1) { f_site += e->sum_log_didl / Nd; f_edge += e->sum_log_didl / (2.0 * Nd); }
+        if (f || parts) {
+            const double sums[4] = {row[0], row[1], 0.0, 0.0}, adj[2] = {row[EM_ADJ], 0.0};
+            double p4[4], all[2] = {0.0, 0.0}, ne[2] = {0.0, 0.0};
+            site_edge_parts(N, e->dc == 1 ? &e->sum_log_didl : nullptr, sums, p4);
             if (nonedge) {
-                double all0 = 0.0;
-                if (exact) {
-                    all0 = row[NP];
-                } else {
-                    const double *wmat = h_mats + size_t(r) * 3 * QQ2;
-                    double Nk = 1.0;
-                    size_t off = 0, tsz = 1;
-                    for (int k = 1; k <= Kr[r]; ++k) {
-                        tsz *= Q;
-                        Nk *= Nd;
-                        std::vector<const double *> ms(k, wmat);
-                        all0 -= contract(row + NP + off, Q, unsigned(k), ms) / (double(k) * Nk);
-                        off += tsz;
-                    }
-                }
-                f_non = (all0 - row[EM_ADJ]) / (2.0 * Nd);
+                if (exact) all[0] = row[NP];
+                else nonedge_series(Q, N, Kr[r], false, row + NP, h_mats + size_t(r) * 3 * QQ2, all);
+                nonedge_finish(all, adj, N, ne);
             }
-            if (parts) { parts[3 * size_t(r)] = f_site; parts[3 * size_t(r) + 1] = f_edge; parts[3 * size_t(r) + 2] = f_non; }
-            if (f) f[r] = -f_site + f_edge + f_non;
+            const double fp[3] = {p4[0], p4[1], ne[0]};
+            if (parts) std::copy(fp, fp + 3, parts + 3 * size_t(r));
+            if (f) f[r] = free_energy_of(fp);
         }
     }
     return SBMBP_OK;

@@ -5,6 +5,8 @@
 // Also the host drivers every front end shares: the segment plan (host_graph.h) against hand-worked tables and its
 // invariants, the batch planner against hand-worked values, and the queue-ahead loop, the convergence run and the EM loop
 // (host_loops.h) over scripted fakes, call for call against traces recorded from the loops they replaced (loop_fakes.h).
+// And the reduction arithmetic they share (host_reduce.h): hand-derivable tables, the moment series against the oracle's at
+// every order, and every function bit for bit against what the copies it replaced gave on fixed inputs (parent_reduce.inc).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -17,6 +19,7 @@
 
 #include "../../sbm-bp_amd/csrc/host_graph.h"
 #include "../../sbm-bp_amd/csrc/host_loops.h"
+#include "../../sbm-bp_amd/csrc/host_reduce.h"
 #include "loop_fakes.h"
 
 extern "C" {
@@ -38,6 +41,7 @@ int orc_bp_converge_async(void *s, float crit, unsigned tmax, float damp, void *
 int orc_bp_converge_sync(void *s, double crit, unsigned tmax, double damp, double *last);
 double orc_bp_free_energy(void *s, int series_K, double *parts);
 double orc_bp_entropy(void *s, int series_K, double *parts);
+void orc_bp_nonedge(void *s, int series_K, double *out);
 void orc_bp_em_expect(void *s, double *na_e, double *nna_e, double *cab_e);
 double orc_bp_overlap(void *s);
 int orc_bp_learning(void *s, float lcrit, unsigned tmax, float lr, float damp, void *rng, int sync, int series_K, double *f);
@@ -430,6 +434,245 @@ static int test_loops() {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------ reduction arithmetic
+static int test_reduce_tables() {
+    using namespace sbmbp;
+    // the 5120-entry budget: 8 + 64 + 512 + 4096 = 4680, 16 + 256 + 4096 = 4368, 17 + 289 + 4913 = 5219 > 5120
+    const uint32_t qs[] = {2, 8, 9, 16, 17, 64};
+    const int caps[] = {4, 4, 3, 3, 2, 2};
+    for (int i = 0; i < 6; ++i) REQUIRE(max_series_order(qs[i]) == caps[i]);
+    REQUIRE(series_len(8, 4) == 4680 && series_len(16, 3) == 4368 && series_len(17, 3) == 5219 && series_len(64, 2) == 4160);
+    REQUIRE(series_len(5, 0) == 0 && series_len(5, 1) == 5);
+    // a requested order is honoured and clamped to the cap
+    REQUIRE(series_order(2, 1000000, 3, 100.0) == 3 && series_order(2, 1000000, 7, 0.1) == 4 && series_order(9, 1000000, 4, 0.1) == 3);
+    // N = 1e6: order 1 leaves wmax^2 / 4N, order 2 wmax^3 / 6N^2 (< 1e-12 below wmax = 6^(1/3) = 1.817), order 3 wmax^4 / 8N^3
+    REQUIRE(series_order(2, 1000000, 0, 1.8) == 2 && series_order(2, 1000000, 0, 1.85) == 3);
+    REQUIRE(series_order(2, 1000000, 0, 1e-4) == 1);
+    // Q = 17, N = 4e4, wmax = 10: the cap's order 2 leaves 1e3 / (6 * 1.6e9) = 1e-7, no order meets the bound
+    REQUIRE(series_order(17, 40000, 0, 10.0) == 2);
+    for (uint32_t N : {32768u, 32769u}) {
+        REQUIRE(nonedge_is_exact(0, N) == (N == 32768));
+        REQUIRE(nonedge_is_exact(1, N) && !nonedge_is_exact(2, N));
+    }
+    {
+        const double sums[4] = {8, 16, 2, 4}, c = 4;
+        double p[4];
+        site_edge_parts(4, nullptr, sums, p);
+        REQUIRE(p[0] == 2 && p[1] == 2 && p[2] == 0.5 && p[3] == 0.5);
+        site_edge_parts(4, &c, sums, p);  // the dc 1 constant: + c / N and + c / 2N, the entropy twin untouched
+        REQUIRE(p[0] == 3 && p[1] == 2.5 && p[2] == 0.5 && p[3] == 0.5);
+        const double fp[3] = {3, 2.5, 0.25}, ep[3] = {0.5, 0.75, 0.5};
+        REQUIRE(free_energy_of(fp) == -0.25 && entropy_of(ep) == -0.25);
+        const double all[2] = {10, 7}, adj[2] = {2, 3};
+        double ne[2];
+        nonedge_finish(all, adj, 4, ne);
+        REQUIRE(ne[0] == 1 && ne[1] == 0.5);
+    }
+    {   // numerators (0,0), (0,1), (1,1) = 3, 5, 7 at N = 10
+        const double tri[3] = {3, 5, 7}, na0[2] = {4, 0}, na[2] = {4, 8}, nna[2] = {8, 16};
+        double ce[4];
+        em_rescale(2, 10, 0, na0, nna, tri, ce);  // label 1 has no mass: only (0,0) is scaled, by 2 N / (4 * 4)
+        REQUIRE(ce[0] == 3.75 && ce[1] == 5 && ce[2] == 5 && ce[3] == 7);
+        em_rescale(2, 10, 0, na, nna, tri, ce);   // dc 0 divides by na: 3 * 20 / 16, 5 * 10 / 32, 7 * 20 / 64
+        REQUIRE(ce[0] == 3.75 && ce[1] == 1.5625 && ce[2] == 1.5625 && ce[3] == 2.1875);
+        em_rescale(2, 10, 1, na, nna, tri, ce);   // dc 1 by nna: 3 * 20 / 64, 5 * 10 / 128, 7 * 20 / 256
+        REQUIRE(ce[0] == 0.9375 && ce[1] == 0.390625 && ce[2] == 0.390625 && ce[3] == 0.546875);
+    }
+    for (uint32_t Q : {3u, 9u}) {  // 1 on the diagonal, 5 one step to the right of it: the cyclic shift collects 5 Q, the identity Q
+        std::vector<double> C(Q * Q, 0.0);
+        for (uint32_t a = 0; a < Q; ++a) { C[a * Q + a] = 1; C[a * Q + (a + 1) % Q] = 5; }
+        REQUIRE(best_overlap(Q, 20, C.data()) == (Q == 3 ? 15.0 / 20.0 : 9.0 / 20.0));
+    }
+    {
+        const double nanv = std::nan(""), f[4] = {-1.0, nanv, -3.0, -2.0};
+        const int r0[4] = {1, 0, 1, 0}, r1[4] = {1, 0, 1, 1};
+        REQUIRE(best_replica(4, f, r0, 2) == 3 && best_replica(4, f, r1, 2) == 2 && best_replica(1, f + 1, r0 + 1, 2) == 0);
+    }
+    return 0;
+}
+
+// the oracle's converged marginals on a shipped graph; moment tensors and adjacent-pair sums formed here with plain loops in
+// row order; {f_nonedge, e_nonedge} through host_reduce.h against the oracle's series at every order the engine can take
+static int test_reduce_against_oracle(const std::string &path, uint32_t N, uint32_t Q, double eps, double c) {
+    using namespace sbmbp;
+    void *og = orc_graph_load_edgelist(path.c_str(), N);
+    REQUIRE(orc_graph_n(og) == N && orc_graph_e2(og) > 0);
+    const uint64_t E2 = orc_graph_e2(og);
+    std::vector<uint64_t> rp(size_t(N) + 1);
+    std::vector<uint32_t> nbr(E2), rev(E2), tc(N), na(Q);
+    orc_graph_copy(og, rp.data(), nbr.data(), rev.data());
+    for (uint32_t i = 0; i < N; ++i) tc[i] = uint32_t(uint64_t(i) * Q / N);
+    std::vector<double> cab(Q * Q), psi(size_t(N) * Q), msg(E2 * Q);
+    orc_param_from_epsilon_c(N, Q, eps, c, cab.data(), na.data());
+    void *bp = orc_bp_create(og, Q, 0);
+    void *rng = orc_rng_create(1);
+    orc_bp_init_messages(bp, 0, nullptr, tc.data(), rng);
+    orc_bp_set_params(bp, cab.data(), na.data(), 1.0);
+    double last = 1.0;
+    REQUIRE(orc_bp_converge_sync(bp, 1e-9, 2000, 1.0, &last) >= 0 && last < 1e-9);
+    orc_bp_get_state(bp, psi.data(), msg.data());
+    std::vector<double> mats(3 * Q * Q), v(Q * Q);
+    double wmax = 0.0;
+    nonedge_mats(Q, N, cab.data(), 1.0, mats.data(), &wmax);
+    REQUIRE(wmax >= *std::max_element(cab.begin(), cab.end()));
+    const double *wmat = mats.data(), *cabm = mats.data() + 2 * Q * Q;
+    for (uint32_t a = 0; a < Q * Q; ++a) v[a] = cabm[a] * std::log(cabm[a]);
+    const int Kmax = max_series_order(Q);
+    std::vector<double> Mk(series_len(Q, Kmax), 0.0), t, tn;
+    for (uint32_t i = 0; i < N; ++i) {  // M_k[a_0 + Q a_1 + ...] = sum_i psi_i[a_0] psi_i[a_1] ...
+        const double *p = psi.data() + size_t(i) * Q;
+        t.assign(1, 1.0);
+        size_t off = 0;
+        for (int k = 1; k <= Kmax; ++k) {
+            tn.resize(t.size() * Q);
+            for (size_t rest = 0; rest < t.size(); ++rest)
+                for (uint32_t a = 0; a < Q; ++a) tn[a + Q * rest] = p[a] * t[rest];
+            t.swap(tn);
+            for (size_t x = 0; x < t.size(); ++x) Mk[off + x] += t[x];
+            off += t.size();
+        }
+    }
+    double adj[2] = {0.0, 0.0};
+    for (uint32_t i = 0; i < N; ++i)
+        for (uint64_t k = rp[i]; k < rp[i + 1]; ++k) {
+            const double *pi = psi.data() + size_t(i) * Q, *pl = psi.data() + size_t(nbr[k]) * Q;
+            double y = 0.0, u = 0.0, yc = 0.0;
+            for (uint32_t a = 0; a < Q; ++a)
+                for (uint32_t b = 0; b < Q; ++b) {
+                    const double pp = pi[a] * pl[b];
+                    y += wmat[a * Q + b] * pp;
+                    u += v[a * Q + b] * pp;
+                    yc += cabm[a * Q + b] * pp;
+                }
+            adj[0] += std::log1p(-y / N);
+            adj[1] += (u / N) / (1.0 - yc / N);
+        }
+    double worst = 0.0;
+    for (int K = 1; K <= Kmax; ++K) {
+        double all[2], got[2], want[2];
+        nonedge_series(Q, N, K, true, Mk.data(), mats.data(), all);
+        nonedge_finish(all, adj, N, got);
+        orc_bp_nonedge(bp, K, want);
+        for (int x = 0; x < 2; ++x) {
+            const double rel = std::fabs(got[x] - want[x]) / std::max(1.0, std::fabs(want[x]));
+            worst = std::max(worst, rel);
+            if (!(rel <= 1e-11)) {
+                std::fprintf(stderr, "host_sanitize: non-edge series Q=%u K=%d part %d: %.17g, the oracle %.17g (relative %.3g)\n", Q, K, x, got[x], want[x], rel);
+                return 1;
+            }
+        }
+        double f_only[2];  // without the entropy the free-energy half is the same number
+        nonedge_series(Q, N, K, false, Mk.data(), mats.data(), f_only);
+        REQUIRE(f_only[0] == all[0] && f_only[1] == 0.0);
+    }
+    std::printf("host_sanitize: non-edge series Q=%u, orders 1..%d against the oracle: largest relative difference %.3g\n", Q, Kmax, worst);
+    orc_rng_free(rng);
+    orc_bp_free(bp);
+    orc_graph_free(og);
+    return 0;
+}
+
+// Fixed inputs of the bit-for-bit comparison: N of the whole graph is not the rows of a shard, beta is not 1.
+struct reduce_case {
+    uint32_t Q, N;
+    double beta, dc1, sums[4], adj[2];
+    std::vector<double> cab, Mk, na, nna, tri, C;
+};
+static reduce_case make_reduce_case(uint32_t Q) {
+    reduce_case c;
+    c.Q = Q;
+    c.N = 50021;  // (three shards of 16674, 16674 and 16673 rows)
+    c.beta = 0.8;
+    uint64_t s = 0x9e3779b97f4a7c15ull * Q;
+    auto u = [&]() { s = s * 6364136223846793005ull + 1442695040888963407ull; return double(s >> 11) * (1.0 / 9007199254740992.0); };
+    c.cab.resize(Q * Q);
+    for (uint32_t a = 0; a < Q; ++a)
+        for (uint32_t b = a; b < Q; ++b) c.cab[a * Q + b] = c.cab[b * Q + a] = (a == b ? 9.25 : 1.75) + 0.5 * u();
+    const int Kmax = sbmbp::max_series_order(Q);
+    c.Mk.resize(sbmbp::series_len(Q, Kmax));
+    size_t off = 0, tsz = 1;
+    for (int k = 1; k <= Kmax; ++k) {
+        tsz *= Q;
+        for (size_t x = 0; x < tsz; ++x) c.Mk[off + x] = double(c.N) * (0.5 + u()) / double(tsz);
+        off += tsz;
+    }
+    c.na.resize(Q); c.nna.resize(Q);
+    for (uint32_t q = 0; q < Q; ++q) { c.na[q] = double(c.N) * (0.5 + u()) / Q; c.nna[q] = 6.5 * c.na[q] * (0.9 + 0.2 * u()); }
+    c.tri.resize(Q * (Q + 1) / 2);
+    for (double &x : c.tri) x = 40.0 * u();
+    c.C.resize(Q * Q);
+    for (double &x : c.C) x = double(c.N) * u() / Q;
+    for (double &x : c.sums) x = -3.0 * double(c.N) * (0.5 + u());
+    for (double &x : c.adj) x = -7.0 * (0.5 + u());
+    c.dc1 = 2.0 * double(c.N) * (1.0 + u());
+    return c;
+}
+
+// every value host_reduce.h computes from a case, in the order parent_reduce.inc holds them
+static std::vector<double> reduce_values(const reduce_case &c) {
+    using namespace sbmbp;
+    const uint32_t Q = c.Q, N = c.N;
+    std::vector<double> out, mats(3 * Q * Q);
+    double wmax = 0.0;
+    nonedge_mats(Q, N, c.cab.data(), c.beta, mats.data(), &wmax);
+    out = mats;
+    out.push_back(wmax);
+    const int Kmax = max_series_order(Q);
+    for (double wm : {wmax, 0.5, 40.0, 3000.0})
+        for (int req = 0; req <= 5; ++req) out.push_back(double(series_order(Q, N, req, wm)));
+    for (int K = 0; K <= Kmax; ++K) out.push_back(double(series_len(Q, K)));
+    double ne[2] = {0.0, 0.0};
+    for (int K = 1; K <= Kmax; ++K)
+        for (int ent = 0; ent < 2; ++ent) {
+            double all[2];
+            nonedge_series(Q, N, K, ent != 0, c.Mk.data(), mats.data(), all);
+            nonedge_finish(all, c.adj, N, ne);
+            out.insert(out.end(), {all[0], all[1], ne[0], ne[1]});
+        }
+    for (int dc1 = 0; dc1 < 2; ++dc1) {  // (ne: the last series above, highest order with the entropy)
+        double p[4];
+        site_edge_parts(N, dc1 ? &c.dc1 : nullptr, c.sums, p);
+        const double fp[3] = {p[0], p[1], ne[0]}, ep[3] = {p[2], p[3], ne[1]};
+        out.insert(out.end(), {p[0], p[1], p[2], p[3], free_energy_of(fp), entropy_of(ep)});
+    }
+    for (uint32_t dc = 0; dc < 2; ++dc) {
+        std::vector<double> ce(Q * Q, 0.0);
+        em_rescale(Q, N, dc, c.na.data(), c.nna.data(), c.tri.data(), ce.data());
+        out.insert(out.end(), ce.begin(), ce.end());
+    }
+    out.push_back(best_overlap(Q, N, c.C.data()));
+    return out;
+}
+
+static int test_reduce_against_parent() {
+    static const char *const expected[] = {  // hex floats as text: C++14 has no hexadecimal floating literal
+#include "parent_reduce.inc"
+    };
+    const size_t n_expected = sizeof expected / sizeof expected[0];
+    size_t at = 0;
+    for (uint32_t Q : {2u, 5u, 16u}) {
+        const std::vector<double> got = reduce_values(make_reduce_case(Q));
+        REQUIRE(at + got.size() <= n_expected);
+        for (size_t i = 0; i < got.size(); ++i, ++at) {
+            const double want = std::strtod(expected[at], nullptr);
+            if (std::memcmp(&got[i], &want, 8) != 0) {
+                std::fprintf(stderr, "host_sanitize: reduce case Q=%u value %zu: %a, the replaced code gave %s\n", Q, i, got[i], expected[at]);
+                return 1;
+            }
+        }
+    }
+    REQUIRE(at == n_expected);
+    return 0;
+}
+
+static int test_reduce(const char *dataset) {
+    const std::string dir = std::string(dataset).substr(0, std::string(dataset).find_last_of('/') + 1);
+    if (test_reduce_tables() != 0) return 1;
+    if (test_reduce_against_oracle(dir + "q4_n400.edgelist", 400, 4, 0.05, 6.0) != 0) return 1;
+    if (test_reduce_against_oracle(dir + "q10_n1000.edgelist", 1000, 10, 0.05, 15.0) != 0) return 1;
+    return test_reduce_against_parent();
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: host_sanitize <edge list of the shipped data set> [--plans <file>]\n"); return 2; }
     if (argc == 4 && std::strcmp(argv[2], "--plans") == 0) {  // the plan comparison alone
@@ -442,6 +685,7 @@ int main(int argc, char **argv) {
     if (rc == 0) rc = test_segment_plan(argv[1]);
     if (rc == 0) rc = test_planner();
     if (rc == 0) rc = test_loops();
+    if (rc == 0) rc = test_reduce(argv[1]);
     if (rc == 0) std::printf("host_sanitize ok\n");
     return rc;
 }

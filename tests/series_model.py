@@ -19,7 +19,7 @@ MOMENT_ENTRIES = 5120
 
 
 def max_series_order(Q):
-    """restatement of engine.hip max_series_order: 4 up to Q = 8, 3 for Q = 9 .. 16, 2 for Q = 17 .. 64"""
+    """restatement of host_reduce.h max_series_order: 4 up to Q = 8, 3 for Q = 9 .. 16, 2 for Q = 17 .. 64"""
     K, T, sz = 0, 0, 1
     while K < 4:
         sz *= Q
@@ -36,7 +36,7 @@ def series_bound(N, wmax, K):
 
 
 def choose_series_order(N, Q, cab, beta):
-    """restatement of engine.hip choose_series_order for the automatic mode: the smallest K whose bound is below 1e-12,
+    """restatement of host_reduce.h series_order for the automatic mode: the smallest K whose bound is below 1e-12,
     else (silently) the cap of the label count. wmax = max over entries of max(w, cab)."""
     Kmax = max_series_order(Q)
     w = nonedge_mats(N, cab, beta)[0]

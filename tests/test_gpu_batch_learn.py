@@ -157,7 +157,7 @@ def test_series_order_is_per_replica(S, orc):
     Q, N = inst["Q"], inst["N"]
     scales = (1.0, 0.01, 0.001)
 
-    def order(cab):  # engine.hip: choose_series_order
+    def order(cab):  # host_reduce.h: series_order
         wmax = max((N * (1.0 - (1.0 - cab / N))).max(), cab.max())
         return next((K for K in range(1, 5) if N * (wmax / N) ** (K + 1) / (2.0 * (K + 1)) < 1e-12), 4)
 

@@ -440,3 +440,52 @@ def test_full_size_c3_two_shards_equal_one(S):
     (d1, o1, f1, r1), (d2, o2, f2, r2) = out
     assert np.abs(np.array(d1) - np.array(d2)).max() < 1e-12 and abs(o1 - o2) < 1e-12
     assert abs(f1 - f2) < 1e-10 * abs(f1) and np.abs(r1 - r2).max() < 1e-9 * N
+
+
+_SERIES_N = 32_769  # the smallest graph whose automatic non-edge term is the moment series (exact loop up to 32 768)
+_series_single = {}
+
+
+def _series_problem(S, Q):
+    """planted partition at N = 32 769, c = 3, dc 0, and the single engine's parts after three sweeps (computed once per Q)"""
+    from sbm_bp_amd import synth
+    N = _SERIES_N
+    pairs, cin, cout = synth.planted_partition(N, Q, 3.0, 0.1, 40 + Q)
+    g = S.Graph.from_edges(pairs, N)
+    cab, na, tc = synth.cab_matrix(Q, cin, cout), np.array(synth.group_sizes(N, Q), dtype=np.uint32), synth.true_conf(N, Q)
+    if Q not in _series_single:
+        bp = S.bp_conditional()
+        bp.init_messages(S.blockmodel_t(g, Q, 0), 0, None, tc, 40 + Q)
+        bp.expand_bp_params(S.bp_blockmodel_state(cab, na))
+        for _ in range(3):
+            bp.sweep(1, 1.0)
+        _series_single[Q] = (bp.compute_free_energy(parts=True), bp.compute_entropy(parts=True))
+    return g, cab, na, tc, _series_single[Q]
+
+
+@pytest.mark.parametrize("world", [1, 3])
+@pytest.mark.parametrize("Q", [2, 4])
+def test_sharded_series_at_the_smallest_size_that_reaches_it(S, Q, world):
+    """sbmbp_shard_nonedge_partial / _finish (moments of the own rows, adjacent pairs, all-reduce, series on the host) one
+    vertex above the exact/series switch, against the single engine on the same sweeps: both in automatic mode, hence the
+    series at the same order. Every other small sharded test has N <= 32 768 and takes the exact branch."""
+    import series_model as sm
+    from sbm_bp_amd.distributed import LocalShards
+    g, cab, na, tc, ((f1, fp1), (e1, ep1)) = _series_problem(S, Q)
+    assert g.N == _SERIES_N > 32_768 and 1 <= sm.choose_series_order(g.N, Q, cab, 1.0) <= sm.max_series_order(Q)
+    sb = LocalShards(g, Q, 0, world)
+    try:
+        sb.init_messages(0, None, tc, 40 + Q, True)
+        sb.expand_bp_params(cab, na, 1.0)
+        for _ in range(3):
+            sb.sweep(1, 1.0)
+        fk, fpk = sb.compute_free_energy(parts=True)
+        ek, epk = sb.compute_entropy(parts=True)
+    finally:
+        sb.close()
+    fp1, fpk, ep1, epk = (np.asarray(x, dtype=np.float64) for x in (fp1, fpk, ep1, epk))
+    print("sharded series Q=%d world=%d: |df parts| %.3g, |de parts| %.3g" % (Q, world, np.abs(fpk - fp1).max(), np.abs(epk - ep1).max()))
+    assert np.abs(fpk - fp1).max() < 1e-10 * max(1.0, np.abs(fp1).max())
+    assert np.abs(epk - ep1).max() < 1e-10 * max(1.0, np.abs(ep1).max())
+    # the totals are sums of three parts, each inside its bound
+    assert abs(fk - f1) < 3e-10 * max(1.0, np.abs(fp1).max()) and abs(ek - e1) < 3e-10 * max(1.0, np.abs(ep1).max())
