@@ -292,6 +292,33 @@ static int test_plans_from_file(const char *path, size_t *count) {
     return 0;
 }
 
+// Chunked plans worked out elsewhere (tests/shard_boundary_graph.py chunked_segment_model on the rows of every rank of the
+// shard recipes, cut as tests/plan_model.py cuts them): per plan one line `cap rcap n n_chunks n_bounds n_hubs`, then the n
+// degrees, the n_chunks + 1 chunk boundaries, the segment boundaries, the hub rows, and chunk_blk and chunk_hub (n_chunks + 1
+// each). segment_plan with these chunk boundaries must give exactly these tables, and pass its invariants.
+static int test_chunk_plans_from_file(const char *path, size_t *count) {
+    std::ifstream f(path);
+    REQUIRE(f.good());
+    uint32_t cap, rcap, n, nc, nb, nh;
+    for (*count = 0; f >> cap >> rcap >> n >> nc >> nb >> nh; ++*count) {
+        u32s deg(n), chunks(nc + 1), bounds(nb), hubs(nh), cblk(nc + 1), chub(nc + 1);
+        for (u32s *v : {&deg, &chunks, &bounds, &hubs, &cblk, &chub}) for (uint32_t &x : *v) REQUIRE(bool(f >> x));
+        std::vector<uint64_t> rp(size_t(n) + 1, 0);
+        for (uint32_t i = 0; i < n; ++i) rp[i + 1] = rp[i] + deg[i];
+        sbmbp::segment_plan_t p;
+        REQUIRE(check_plan(rp, n, cap, rcap, chunks, p) == 0);
+        const char *what = p.blk_row != bounds ? "blk_row" : p.hub_row != hubs ? "hub_row" : p.chunk_blk != cblk ? "chunk_blk" : p.chunk_hub != chub ? "chunk_hub" : nullptr;
+        if (what) {
+            std::fprintf(stderr, "host_sanitize: chunked plan %zu (cap %u, rcap %u, %u rows, %u chunks): %s differs; segment_plan gives %zu segments and %zu hub rows, the file %zu and %zu\n",
+                         *count, cap, rcap, n, nc, what, p.blk_row.size() - 1, p.hub_row.size(), bounds.size() - 1, hubs.size());
+            return 1;
+        }
+        for (size_t h = 0; h < hubs.size(); ++h) REQUIRE(p.blk_row[p.hub_blk[h]] == hubs[h]);
+    }
+    REQUIRE(f.eof() && *count > 0);
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------ batch planner
 static int test_planner() {
     using sbmbp::batch_planner;
@@ -674,11 +701,17 @@ static int test_reduce(const char *dataset) {
 }
 
 int main(int argc, char **argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: host_sanitize <edge list of the shipped data set> [--plans <file>]\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: host_sanitize <edge list of the shipped data set> [--plans <file> | --chunk-plans <file>]\n"); return 2; }
     if (argc == 4 && std::strcmp(argv[2], "--plans") == 0) {  // the plan comparison alone
         size_t count = 0;
         const int prc = test_plans_from_file(argv[3], &count);
         if (prc == 0) std::printf("host_sanitize ok: %zu plans\n", count);
+        return prc;
+    }
+    if (argc == 4 && std::strcmp(argv[2], "--chunk-plans") == 0) {  // the chunked plan comparison alone
+        size_t count = 0;
+        const int prc = test_chunk_plans_from_file(argv[3], &count);
+        if (prc == 0) std::printf("host_sanitize ok: %zu chunked plans\n", count);
         return prc;
     }
     int rc = run(argv[1]);
