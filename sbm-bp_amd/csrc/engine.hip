@@ -587,64 +587,31 @@ void free_coloured(sbmbp_engine *e) {
     e->cs_bytes = 0;
 }
 
-// Device tables of the coloured order from the step of every vertex (host_graph.cpp coloured_plan): rows ascending inside
-// a step, greedy segments of <= CAP edges and <= RCAP rows with the rows' edge offsets relative to their segment; rows
-// above CAP edges are the step's hubs, numbered in step order with fragments of BLOCK edges (setup_hub_frags).
+// Device tables of the coloured order from the step of every vertex (host_graph.cpp coloured_plan): the tables are
+// coloured_step_tables' (host_graph.cpp), with fragments of BLOCK edges as setup_hub_frags cuts them.
 int build_coloured(sbmbp_engine *e, const std::vector<uint32_t> &step, uint32_t n_colours, uint32_t n_steps) {
     free_coloured(e);
-    const uint32_t N = e->N, cap = uint32_t(frame_cap(e->Q)), rcap = uint32_t(frame_rcap(e->Q));
-    const std::vector<uint32_t> &rp = e->h_row_ptr;
-    std::vector<uint32_t> first(size_t(n_steps) + 1, 0u), by_step(N);
-    for (uint32_t i = 0; i < N; ++i) first[step[i] + 1]++;
-    for (uint32_t s = 0; s < n_steps; ++s) first[s + 1] += first[s];
-    { std::vector<uint32_t> pos(first.begin(), first.end() - 1); for (uint32_t i = 0; i < N; ++i) by_step[pos[step[i]]++] = i; }
-    std::vector<uint32_t> rows, loff, seg_row0(1, 0u), hub_row, hub_rec, frag_hub, hub_frag0(1, 0u);
-    rows.reserve(N); loff.reserve(size_t(N) + N / 8 + 16);
-    e->cs_seg0.assign(1, 0u); e->cs_hub0.assign(1, 0u); e->cs_frag0.assign(1, 0u);
-    uint32_t max_rec = 1;
-    for (uint32_t s = 0; s < n_steps; ++s) {
-        uint32_t nr = 0, ne = 0;
-        const uint32_t seg_first = uint32_t(seg_row0.size() - 1);
-        auto close_seg = [&]() { if (nr) { loff.push_back(ne); seg_row0.push_back(uint32_t(rows.size())); nr = 0; ne = 0; } };
-        for (uint32_t x = first[s]; x < first[s + 1]; ++x) {
-            const uint32_t i = by_step[x], d = rp[i + 1] - rp[i];
-            if (d > cap) { hub_row.push_back(i); continue; }
-            if (nr + 1 > rcap || ne + d > cap) close_seg();
-            rows.push_back(i);
-            loff.push_back(ne);
-            ++nr; ne += d;
-        }
-        close_seg();
-        const uint32_t nseg = uint32_t(seg_row0.size() - 1) - seg_first;
-        for (size_t h = e->cs_hub0.back(); h < hub_row.size(); ++h) {  // the step's records: its segments, then its hubs
-            hub_rec.push_back(nseg + uint32_t(h - e->cs_hub0.back()));
-            const uint32_t d = rp[hub_row[h] + 1] - rp[hub_row[h]];
-            for (uint32_t k = 0; k < (d + BLOCK - 1) / BLOCK; ++k) frag_hub.push_back(uint32_t(h));
-            hub_frag0.push_back(uint32_t(frag_hub.size()));
-        }
-        max_rec = std::max<uint32_t>(max_rec, nseg + uint32_t(hub_row.size() - e->cs_hub0.back()));
-        e->cs_seg0.push_back(uint32_t(seg_row0.size() - 1));
-        e->cs_hub0.push_back(uint32_t(hub_row.size()));
-        e->cs_frag0.push_back(uint32_t(frag_hub.size()));
-    }
-    if (frag_hub.size() != e->n_frag) { set_error("coloured order: fragment tables disagree"); return SBMBP_ERR_STATE; }
+    coloured_tables_t t;
+    coloured_step_tables(e->h_row_ptr.data(), e->N, step.data(), n_steps, uint32_t(frame_cap(e->Q)), uint32_t(frame_rcap(e->Q)), uint32_t(BLOCK), t);
+    if (t.frag_hub.size() != e->n_frag) { set_error("coloured order: fragment tables disagree"); return SBMBP_ERR_STATE; }
     auto up = [&](uint32_t **d, const std::vector<uint32_t> &h) -> int {
         CHK(dev_alloc(e, d, h.size()));
         e->cs_bytes += std::max<size_t>(h.size(), 1) * 4;
         if (!h.empty()) HIPCHK(hipMemcpyAsync(*d, h.data(), h.size() * 4, hipMemcpyHostToDevice, e->stream));
         return SBMBP_OK;
     };
-    CHK(up(&e->d_cs_rows, rows));
-    CHK(up(&e->d_cs_loff, loff));
-    CHK(up(&e->d_cs_seg_row0, seg_row0));
-    CHK(up(&e->d_cs_hub_row, hub_row));
-    CHK(up(&e->d_cs_hub_rec, hub_rec));
-    CHK(up(&e->d_cs_frag_hub, frag_hub));
-    CHK(up(&e->d_cs_hub_frag0, hub_frag0));
+    CHK(up(&e->d_cs_rows, t.rows));
+    CHK(up(&e->d_cs_loff, t.loff));
+    CHK(up(&e->d_cs_seg_row0, t.seg_row0));
+    CHK(up(&e->d_cs_hub_row, t.hub_row));
+    CHK(up(&e->d_cs_hub_rec, t.hub_rec));
+    CHK(up(&e->d_cs_frag_hub, t.frag_hub));
+    CHK(up(&e->d_cs_hub_frag0, t.hub_frag0));
     HIPCHK(hipStreamSynchronize(e->stream));  // the tables are locals
     e->cs_colours = n_colours;
     e->cs_steps = n_steps;
-    e->cs_max_rec = max_rec;
+    e->cs_seg0.swap(t.seg0); e->cs_hub0.swap(t.hub0); e->cs_frag0.swap(t.frag0);
+    e->cs_max_rec = t.max_rec;
     return SBMBP_OK;
 }
 

@@ -636,6 +636,47 @@ void segment_plan(const uint64_t *row_ptr, uint32_t n, uint32_t cap, uint32_t rc
     for (size_t b = 0; b < blk_row.size(); ++b) out.blk_e0[b] = uint32_t(row_ptr[blk_row[b]]);
 }
 
+void coloured_step_tables(const uint32_t *rp, uint32_t N, const uint32_t *step, uint32_t n_steps, uint32_t cap, uint32_t rcap,
+                          uint32_t frag, coloured_tables_t &out) {
+    out = coloured_tables_t();
+    std::vector<uint32_t> first(size_t(n_steps) + 1, 0u), by_step(N);
+    for (uint32_t i = 0; i < N; ++i) first[step[i] + 1]++;
+    for (uint32_t s = 0; s < n_steps; ++s) first[s + 1] += first[s];
+    { std::vector<uint32_t> pos(first.begin(), first.end() - 1); for (uint32_t i = 0; i < N; ++i) by_step[pos[step[i]]++] = i; }
+    std::vector<uint32_t> &rows = out.rows, &loff = out.loff, &seg_row0 = out.seg_row0, &hub_row = out.hub_row, &hub_rec = out.hub_rec,
+                          &frag_hub = out.frag_hub, &hub_frag0 = out.hub_frag0;
+    seg_row0.assign(1, 0u); hub_frag0.assign(1, 0u);
+    rows.reserve(N); loff.reserve(size_t(N) + N / 8 + 16);
+    out.seg0.assign(1, 0u); out.hub0.assign(1, 0u); out.frag0.assign(1, 0u);
+    uint32_t max_rec = 1;
+    for (uint32_t s = 0; s < n_steps; ++s) {
+        uint32_t nr = 0, ne = 0;
+        const uint32_t seg_first = uint32_t(seg_row0.size() - 1);
+        auto close_seg = [&]() { if (nr) { loff.push_back(ne); seg_row0.push_back(uint32_t(rows.size())); nr = 0; ne = 0; } };
+        for (uint32_t x = first[s]; x < first[s + 1]; ++x) {
+            const uint32_t i = by_step[x], d = rp[i + 1] - rp[i];
+            if (d > cap) { hub_row.push_back(i); continue; }
+            if (nr + 1 > rcap || ne + d > cap) close_seg();
+            rows.push_back(i);
+            loff.push_back(ne);
+            ++nr; ne += d;
+        }
+        close_seg();
+        const uint32_t nseg = uint32_t(seg_row0.size() - 1) - seg_first;
+        for (size_t h = out.hub0.back(); h < hub_row.size(); ++h) {  // the step's records: its segments, then its hubs
+            hub_rec.push_back(nseg + uint32_t(h - out.hub0.back()));
+            const uint32_t d = rp[hub_row[h] + 1] - rp[hub_row[h]];
+            for (uint32_t k = 0; k < (d + frag - 1) / frag; ++k) frag_hub.push_back(uint32_t(h));
+            hub_frag0.push_back(uint32_t(frag_hub.size()));
+        }
+        max_rec = std::max<uint32_t>(max_rec, nseg + uint32_t(hub_row.size() - out.hub0.back()));
+        out.seg0.push_back(uint32_t(seg_row0.size() - 1));
+        out.hub0.push_back(uint32_t(hub_row.size()));
+        out.frag0.push_back(uint32_t(frag_hub.size()));
+    }
+    out.max_rec = max_rec;
+}
+
 // bp.cpp:58-63 truncates lr*na_expect + (1-lr)*na to an integer. na_expect is a sum of N marginals, each known to
 // the BP criterion, so a value within snap = min(learn_snap * N * crit, 0.01) below an integer is that integer as
 // far as the fixed point is known (README run: 500 - 9e-5 with the relaxed field, 500 - 1.6e-7 without, on a

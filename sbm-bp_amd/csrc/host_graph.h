@@ -61,6 +61,21 @@ struct segment_plan_t {
 void segment_plan(const uint64_t *row_ptr, uint32_t n, uint32_t cap, uint32_t rcap, const std::vector<uint32_t> &chunk_row,
                   segment_plan_t &out);
 
+// The tables of the coloured order from the step of every vertex (coloured_plan): rows ascending inside a step, greedy
+// segments of at most cap edges and rcap rows; a row above cap is a hub of its step, set aside WITHOUT closing the open
+// segment. Segment b (numbered over all steps) holds rows[seg_row0[b] .. seg_row0[b + 1]]; loff holds, per segment, the
+// edge offset of each of its rows relative to the segment and then the segment's edge total, so the block of segment b
+// starts at loff[seg_row0[b] + b]. Hubs are numbered in step order: hub h is row hub_row[h], writes record hub_rec[h] =
+// (segments of its step) + (its index among the step's hubs) and owns fragments hub_frag0[h] .. hub_frag0[h + 1] of `frag`
+// edges, frag_hub[f] = hub of fragment f. Step s owns segments seg0[s] .. seg0[s + 1], hubs hub0[s] .. hub0[s + 1] and
+// fragments frag0[s] .. frag0[s + 1]; max_rec = the most records (segments + hubs) of any step, at least 1.
+struct coloured_tables_t {
+    std::vector<uint32_t> rows, loff, seg_row0, hub_row, hub_rec, frag_hub, hub_frag0, seg0, hub0, frag0;
+    uint32_t max_rec = 1;
+};
+void coloured_step_tables(const uint32_t *row_ptr, uint32_t n, const uint32_t *step, uint32_t n_steps, uint32_t cap, uint32_t rcap,
+                          uint32_t frag, coloured_tables_t &out);
+
 // learning_step (bp.cpp:53-75): the new group sizes and affinities of one EM step, in place in na / cab
 void learning_step_host(uint32_t Q, uint32_t N, double learning_rate, double learn_snap, double crit, const double *na_e,
                         const double *cab_e, uint32_t *na, double *cab);

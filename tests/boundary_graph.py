@@ -48,8 +48,8 @@ def segment_model(deg, cap, rcap):
 
 
 def step_segment_model(deg, rows, cap, rcap):
-    """the segments of one step of the coloured order (engine.hip build_coloured) over `rows` (ascending): hub rows are set
-    aside WITHOUT closing the open segment. Returns (list of row lists, hub rows)."""
+    """the segments of one step of the coloured order (csrc/host_graph.cpp coloured_step_tables) over `rows` (ascending): hub
+    rows are set aside WITHOUT closing the open segment. Returns (list of row lists, hub rows)."""
     segs, hubs, cur, edges = [], [], [], 0
     for i in rows:
         d = int(deg[i])
@@ -64,6 +64,42 @@ def step_segment_model(deg, rows, cap, rcap):
     if cur:
         segs.append(cur)
     return segs, hubs
+
+
+def step_plan_model(deg, step, cap, rcap, frag=FRAG):
+    """the tables of the whole coloured order (csrc/host_graph.cpp coloured_step_tables) from the step of every row:
+    step_segment_model step by step. Segments and hubs are numbered over all steps; loff holds per segment the edge offset of
+    each row inside it and then its edge total (so segment b's block starts at loff[seg_row0[b] + b]); a hub's record is the
+    number of segments of its step plus its index among the step's hubs; seg0 / hub0 / frag0 are the first segment, hub and
+    fragment of every step (n_steps + 1 entries); max_rec = the most records (segments + hubs) of a step, at least 1."""
+    step = np.asarray(step, dtype=np.int64)
+    n_steps = int(step.max()) + 1 if len(step) else 0
+    t = dict(rows=[], loff=[], seg_row0=[0], hub_row=[], hub_rec=[], frag_hub=[], hub_frag0=[0], seg0=[0], hub0=[0], frag0=[0], max_rec=1)
+    order = np.argsort(step, kind="stable")
+    first = np.searchsorted(step[order], np.arange(n_steps + 1))
+    for s in range(n_steps):
+        segs, hubs = step_segment_model(deg, order[first[s]:first[s + 1]], cap, rcap)
+        for seg in segs:
+            e = 0
+            for i in seg:
+                t["rows"].append(i)
+                t["loff"].append(e)
+                e += int(deg[i])
+            t["loff"].append(e)
+            t["seg_row0"].append(len(t["rows"]))
+        for k, h in enumerate(hubs):
+            t["hub_rec"].append(len(segs) + k)
+            t["frag_hub"] += [len(t["hub_row"])] * (-(-int(deg[h]) // frag))
+            t["hub_row"].append(h)
+            t["hub_frag0"].append(len(t["frag_hub"]))
+        t["max_rec"] = max(t["max_rec"], len(segs) + len(hubs))
+        t["seg0"].append(len(t["seg_row0"]) - 1)
+        t["hub0"].append(len(t["hub_row"]))
+        t["frag0"].append(len(t["frag_hub"]))
+    return t
+
+
+STEP_TABLES = ("rows", "loff", "seg_row0", "hub_row", "hub_rec", "frag_hub", "hub_frag0", "seg0", "hub0", "frag0")
 
 
 def hub_whole(cap):

@@ -95,11 +95,41 @@ def sweep(ob, step, damp=1.0, clamped=None):
     return md
 
 
-def converge(ob, step, crit, tmax, damp=1.0, clamped=None):
+def fast_sweep(ob, step, damp=1.0, clamped=None):
+    """sweep() with one oracle call per STEP instead of a state copy per row: the state of the step's start is put back
+    (set_state) and the field rebuilt from it (init_h), ONE synchronous sweep updates every row from that frozen state, and
+    only the marginals and out-messages of the step's unclamped rows are kept - _row_by_sync_sweep for the whole step. Same
+    equations as sweep(); the products are rescaled (bp_oracle.cpp sweep_sync), so the two agree to rounding, not bit for bit
+    (tests/test_coloured_step_cpu.py). For graphs of tens of thousands of rows and for whole convergence
+    runs."""
+    step = np.asarray(step)
+    row_ptr = np.asarray(ob.g.row_ptr, dtype=np.int64)
+    edge_step = np.repeat(step, np.diff(row_ptr))
+    keep = np.ones(len(step), dtype=bool) if clamped is None else ~np.asarray(clamped, dtype=bool)
+    edge_keep = np.repeat(keep, np.diff(row_ptr))
+    md = 0.0
+    psi0, msg0 = ob.get_state()
+    for s in range(int(step.max()) + 1 if len(step) else 0):
+        rows, edges = (step == s) & keep, (edge_step == s) & edge_keep
+        if not rows.any():
+            continue
+        ob.set_state(psi0, msg0)
+        ob.init_h()
+        ob.sweep_sync(damp)
+        psi1, msg1 = ob.get_state()
+        md = max(md, np.abs(msg1[edges] - msg0[edges]).max(initial=0.0) / damp)  # a damped message moves by damp * (new - old)
+        psi0[rows] = psi1[rows]
+        msg0[edges] = msg1[edges]
+    ob.set_state(psi0, msg0)
+    ob.init_h()
+    return float(md)
+
+
+def converge(ob, step, crit, tmax, damp=1.0, clamped=None, fast=False):
     """(niter, last difference): 0-based index of the first sweep whose difference is below crit, or -1 after tmax sweeps"""
     last = 0.0
     for it in range(tmax):
-        last = sweep(ob, step, damp, clamped)
+        last = (fast_sweep if fast else sweep)(ob, step, damp, clamped)
         if last < crit:
             return it, last
     return -1, last

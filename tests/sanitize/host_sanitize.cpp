@@ -7,6 +7,8 @@
 // (host_loops.h) over scripted fakes, call for call against traces recorded from the loops they replaced (loop_fakes.h).
 // And the reduction arithmetic they share (host_reduce.h): hand-derivable tables, the moment series against the oracle's at
 // every order, and every function bit for bit against what the copies it replaced gave on fixed inputs (parent_reduce.inc).
+// And the step tables of the coloured order (host_graph.h coloured_step_tables): a hand-worked case, their invariants, and
+// entry for entry what the engine built before the construction became host code (parent_step_tables.inc).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -316,6 +318,107 @@ static int test_chunk_plans_from_file(const char *path, size_t *count) {
         for (size_t h = 0; h < hubs.size(); ++h) REQUIRE(p.blk_row[p.hub_blk[h]] == hubs[h]);
     }
     REQUIRE(f.eof() && *count > 0);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ the coloured order's tables
+// Step plans as a stream of numbers (tests/boundary_graph.py step_plan_model on the layouts of tests/coloured_step_graph.py):
+// per plan `cap rcap n n_steps max_rec` and the lengths of rows, loff, seg_row0, hub_row, hub_rec, frag_hub, hub_frag0, seg0,
+// hub0, frag0; then the n degrees, the step of every row, and the ten tables. coloured_step_tables (fragments of 256 edges)
+// must give exactly these, and pass its invariants.
+static int check_step_plans(const u32s &tok, size_t *count, const char *what) {
+    size_t at = 0;
+    for (*count = 0; at < tok.size(); ++*count) {
+        REQUIRE(at + 15 <= tok.size());
+        const uint32_t cap = tok[at], rcap = tok[at + 1], n = tok[at + 2], n_steps = tok[at + 3], max_rec = tok[at + 4];
+        const uint32_t *len = &tok[at + 5];
+        size_t total = 2 * size_t(n);
+        for (int k = 0; k < 10; ++k) total += len[k];
+        at += 15;
+        REQUIRE(at + total <= tok.size());
+        std::vector<uint32_t> rp(size_t(n) + 1, 0);
+        for (uint32_t i = 0; i < n; ++i) rp[i + 1] = rp[i] + tok[at + i];
+        const u32s step(tok.begin() + at + n, tok.begin() + at + 2 * size_t(n));
+        for (uint32_t s : step) REQUIRE(s < n_steps);
+        at += 2 * size_t(n);
+        sbmbp::coloured_tables_t t;
+        sbmbp::coloured_step_tables(rp.data(), n, step.data(), n_steps, cap, rcap, 256, t);
+        const u32s *got[10] = {&t.rows, &t.loff, &t.seg_row0, &t.hub_row, &t.hub_rec, &t.frag_hub, &t.hub_frag0, &t.seg0, &t.hub0, &t.frag0};
+        static const char *const names[10] = {"rows", "loff", "seg_row0", "hub_row", "hub_rec", "frag_hub", "hub_frag0", "seg0", "hub0", "frag0"};
+        for (int k = 0; k < 10; ++k) {
+            const u32s want(tok.begin() + at, tok.begin() + at + len[k]);
+            at += len[k];
+            if (*got[k] != want) {
+                std::fprintf(stderr, "host_sanitize: %s plan %zu (cap %u, rcap %u, %u rows, %u steps): %s differs (%zu entries, expected %zu)\n", what, *count, cap,
+                             rcap, n, n_steps, names[k], got[k]->size(), want.size());
+                for (size_t i = 0; i < std::min(want.size(), got[k]->size()); ++i)
+                    if ((*got[k])[i] != want[i]) { std::fprintf(stderr, "  first difference: entry %zu is %u, expected %u\n", i, (*got[k])[i], want[i]); break; }
+                return 1;
+            }
+        }
+        if (t.max_rec != max_rec) { std::fprintf(stderr, "host_sanitize: %s plan %zu: max_rec %u, expected %u\n", what, *count, t.max_rec, max_rec); return 1; }
+        // the invariants the kernels rely on
+        const size_t nseg = t.seg_row0.size() - 1, nhub = t.hub_row.size();
+        REQUIRE(t.seg0.size() == size_t(n_steps) + 1 && t.hub0.size() == t.seg0.size() && t.frag0.size() == t.seg0.size());
+        REQUIRE(t.seg0.back() == nseg && t.hub0.back() == nhub && t.frag0.back() == t.frag_hub.size() && t.hub_frag0.size() == nhub + 1);
+        REQUIRE(t.rows.size() + nhub == n && t.loff.size() == t.rows.size() + nseg && t.hub_rec.size() == nhub);
+        for (size_t b = 0; b < nseg; ++b) {  // a segment's block of loff: its rows' offsets, then its edge total
+            const uint32_t r0 = t.seg_row0[b], r1 = t.seg_row0[b + 1];
+            const uint32_t *lo = &t.loff[r0 + b];
+            REQUIRE(r1 > r0 && r1 - r0 <= rcap && lo[0] == 0 && lo[r1 - r0] <= cap);
+            for (uint32_t x = r0; x < r1; ++x) {
+                REQUIRE(lo[x - r0 + 1] - lo[x - r0] == rp[t.rows[x] + 1] - rp[t.rows[x]] && step[t.rows[x]] == step[t.rows[r0]]);
+                REQUIRE(x == r0 || t.rows[x] > t.rows[x - 1]);
+            }
+        }
+        for (uint32_t s = 0; s < n_steps; ++s) {
+            REQUIRE(t.seg0[s] <= t.seg0[s + 1] && t.hub0[s] <= t.hub0[s + 1] && t.frag0[s] == t.hub_frag0[t.hub0[s]]);
+            REQUIRE(t.seg0[s + 1] - t.seg0[s] + t.hub0[s + 1] - t.hub0[s] <= t.max_rec);
+            for (uint32_t b = t.seg0[s]; b < t.seg0[s + 1]; ++b) REQUIRE(step[t.rows[t.seg_row0[b]]] == s);
+            for (uint32_t h = t.hub0[s]; h < t.hub0[s + 1]; ++h) {
+                const uint32_t d = rp[t.hub_row[h] + 1] - rp[t.hub_row[h]];
+                REQUIRE(step[t.hub_row[h]] == s && d > cap && t.hub_rec[h] == t.seg0[s + 1] - t.seg0[s] + h - t.hub0[s]);
+                REQUIRE(t.hub_frag0[h + 1] - t.hub_frag0[h] == (d + 255) / 256);
+                for (uint32_t f = t.hub_frag0[h]; f < t.hub_frag0[h + 1]; ++f) REQUIRE(t.frag_hub[f] == h);
+            }
+        }
+    }
+    REQUIRE(*count > 0);
+    return 0;
+}
+
+static int test_step_plans_from_file(const char *path, size_t *count) {
+    std::ifstream f(path);
+    REQUIRE(f.good());
+    u32s tok;
+    for (uint32_t x; f >> x;) tok.push_back(x);
+    REQUIRE(f.eof());
+    return check_step_plans(tok, count, "step");
+}
+
+static int test_step_tables() {
+    {   // cap 4, rcap 3, fragments of 256 edges, worked out by hand. Rows 0 .. 8 of 1 5 2 2 1 0 6 1 1 edges in steps
+        // 1 0 1 1 1 2 0 1 1: step 0 is the two hubs alone; step 1 packs rows 0 2 | 3 4 7 | 8 (the edge limit, then the row
+        // limit); step 2 is one row without an edge
+        const u32s tok = {4, 3, 9, 3, 3, 7, 11, 5, 2, 2, 2, 3, 4, 4, 4,
+                          1, 5, 2, 2, 1, 0, 6, 1, 1,  1, 0, 1, 1, 1, 2, 0, 1, 1,
+                          0, 2, 3, 4, 7, 8, 5,  0, 1, 3, 0, 2, 3, 4, 0, 1, 0, 0,  0, 2, 5, 6, 7,  1, 6,  0, 1,  0, 1,  0, 1, 2,
+                          0, 0, 3, 4,  0, 2, 2, 2,  0, 2, 2, 2};
+        size_t count = 0;
+        REQUIRE(check_step_plans(tok, &count, "hand-worked") == 0 && count == 1);
+    }
+    {   // no rows, no steps: the sentinels alone
+        sbmbp::coloured_tables_t t;
+        const uint32_t rp0 = 0;
+        sbmbp::coloured_step_tables(&rp0, 0, nullptr, 0, 4, 3, 256, t);
+        REQUIRE(t.rows.empty() && t.loff.empty() && t.seg_row0 == u32s{0} && t.hub_frag0 == u32s{0} && t.seg0 == u32s{0} && t.max_rec == 1);
+    }
+    // what build_coloured (engine.hip) built before the construction moved to host_graph.cpp, on two layouts
+    static const uint32_t parent[] = {
+#include "parent_step_tables.inc"
+    };
+    size_t count = 0;
+    REQUIRE(check_step_plans(u32s(parent, parent + sizeof parent / sizeof parent[0]), &count, "recorded") == 0 && count == 2);
     return 0;
 }
 
@@ -701,7 +804,7 @@ static int test_reduce(const char *dataset) {
 }
 
 int main(int argc, char **argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: host_sanitize <edge list of the shipped data set> [--plans <file> | --chunk-plans <file>]\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: host_sanitize <edge list of the shipped data set> [--plans <file> | --chunk-plans <file> | --step-plans <file>]\n"); return 2; }
     if (argc == 4 && std::strcmp(argv[2], "--plans") == 0) {  // the plan comparison alone
         size_t count = 0;
         const int prc = test_plans_from_file(argv[3], &count);
@@ -714,8 +817,15 @@ int main(int argc, char **argv) {
         if (prc == 0) std::printf("host_sanitize ok: %zu chunked plans\n", count);
         return prc;
     }
+    if (argc == 4 && std::strcmp(argv[2], "--step-plans") == 0) {  // the step tables of the coloured order alone
+        size_t count = 0;
+        const int prc = test_step_plans_from_file(argv[3], &count);
+        if (prc == 0) std::printf("host_sanitize ok: %zu step plans\n", count);
+        return prc;
+    }
     int rc = run(argv[1]);
     if (rc == 0) rc = test_segment_plan(argv[1]);
+    if (rc == 0) rc = test_step_tables();
     if (rc == 0) rc = test_planner();
     if (rc == 0) rc = test_loops();
     if (rc == 0) rc = test_reduce(argv[1]);

@@ -68,7 +68,7 @@ def test_a_dropped_block_fails_its_named_conditions(cap, rcap, drop):
 
 @pytest.mark.parametrize("cap,rcap", bg.CLASSES)
 def test_class_zero_of_the_coloured_order_meets_the_shapes(cap, rcap):
-    """the coloured order sets hub rows aside without closing the open segment (engine.hip build_coloured), so class 0 - all
+    """the coloured order sets hub rows aside without closing the open segment (coloured_step_tables), so class 0 - all
     structured rows - packs differently from the synchronous plan. What it still meets: a full one-row segment, the two rows
     that fill one, a segment of rcap rows, rows of every named length, and all eleven hub rows in one step."""
     g = bg.graph(cap, rcap)
