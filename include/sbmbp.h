@@ -120,6 +120,31 @@ int sbmbp_set_state(sbmbp_engine_t *e, const double *psi /* N*Q or NULL */, cons
 int sbmbp_get_state(sbmbp_engine_t *e, double *psi /* or NULL */, double *msg_out /* or NULL */);
 int sbmbp_get_field(sbmbp_engine_t *e, double *h /* Q */); /* h_ of belief_propagation.cpp:320-360 */
 
+/* Per-vertex label prior (no reference counterpart: the reference knows free vertices and vertices clamped to one label only;
+ * DESIGN.md section 2). prior[N*Q]: doubles >= 0, finite, at least one entry > 0 in every row; stored as given, never
+ * normalised. Row i is updated as without a prior, with eta_q replaced by eta_q * prior[i*Q+q]: in its marginal, in every
+ * message it sends (the cavity) and in the exact cavity product the sweep falls back to when a division is unusable - the
+ * prior acts like the field of one more incoming edge. It also enters the site terms of the free energy and of the entropy;
+ * the field h, the edge and non-edge terms and the EM numerators are formed as before. Scaling row i by a constant c > 0
+ * changes no marginal and no message; it adds log(c)/N to parts[0] (f_site) of sbmbp_free_energy, so the free energy, which
+ * takes f_site with a minus sign, moves by -log(c)/N. A row of ones is "no prior" for that vertex; a zero entry forbids the
+ * label (marginal and out-message entries exactly 0). Clamped rows are not updated, so their prior row is ignored by the sweeps.
+ * The prior belongs to the engine like the graph: it survives sbmbp_init_messages*, sbmbp_set_params and sbmbp_set_state, is
+ * replaced by the next sbmbp_set_vertex_prior and removed by prior == NULL; setting or removing it drops what the engine
+ * caches about the state. sbmbp_learning applies the reference's update rules unchanged with the prior held fixed.
+ * While a prior is set the engine runs the message-gather form only, as for general clamped rows: psi_form_sweeps of
+ * sbmbp_stats does not grow, the reductions take the message-form kernels, and bytes_per_sweep grows by 8 Q N.
+ * SBMBP_ERR_ARG (before any device work; the message names the first offending vertex): a negative, NaN or Inf entry, a row
+ * without a positive entry. SBMBP_ERR_UNSUPPORTED: Q > 16; a shard engine; an engine in the coloured sweep order - and
+ * sbmbp_set_sweep_order(e, 1, ...) on an engine that holds a prior. Replica batches and sbmbp_dist_* take no prior.
+ * sbmbp_get_vertex_prior: *present = 1 and the table copied into prior (N*Q, or NULL) when one is set, else *present = 0.
+ * sbmbp_prior_load: host only, no device. Reads the text format "vertex w_0 ... w_{Q-1}", one line per annotated vertex in any
+ * order, into a dense table (ones where no line names the vertex); *n_rows_given = lines read. SBMBP_ERR_IO: unreadable;
+ * SBMBP_ERR_ARG with the line number: vertex id >= n_vertices, a vertex named twice, a wrong column count, a bad value. */
+int sbmbp_set_vertex_prior(sbmbp_engine_t *e, const double *prior /* N*Q, or NULL: remove */);
+int sbmbp_get_vertex_prior(sbmbp_engine_t *e, double *prior /* N*Q or NULL */, int *present);
+int sbmbp_prior_load(const char *path, uint32_t n_vertices, uint32_t Q, double *prior /* N*Q */, uint64_t *n_rows_given);
+
 /* Schedule of the synchronous sweep (no reference counterpart: the reference is random-sequential,
  * belief_propagation.cpp:394-401). field_mix in (0,1]: relaxation of the global field between
  * sweeps (1 = plain Jacobi). check_every >= 1: sweeps enqueued between two host reads of the

@@ -101,6 +101,16 @@ def load_beliefs(path):
     return np.loadtxt(path, dtype=np.int32, ndmin=1)
 
 
+def load_priors(path, N, Q):
+    """per-vertex prior file (sbmbp.h sbmbp_prior_load): lines "vertex w_0 ... w_{Q-1}" in any order -> dense (N, Q) table,
+    ones where no line names the vertex. A bad file raises SbmbpError (code -5 unreadable, -1 otherwise)"""
+    lib = load_library()
+    pr = np.empty((int(N), int(Q)), dtype=np.float64)
+    given = C.c_uint64(0)
+    check(lib.sbmbp_prior_load(os.fsencode(path), int(N), int(Q), pr.ctypes.data_as(c_dp), C.byref(given)))
+    return pr
+
+
 def load_confs(path):
     """load_confs (graph_utilities.cpp:25-40)"""
     return np.loadtxt(path, dtype=np.uint32, ndmin=1)
@@ -172,6 +182,7 @@ class BeliefPropagation:
         self._beta = 1.0
         self.if_output_marginals_ = False
         self.Q = self.N = self.E2 = 0
+        self._prior = None
 
     def __del__(self):
         try:
@@ -192,6 +203,11 @@ class BeliefPropagation:
         self._h = h
         self._graph = blockmodel.graph  # the reference keeps a raw pointer (belief_propagation.h:27)
         self.Q, self.N, self.E2 = blockmodel.get_Q(), blockmodel.get_N(), blockmodel.graph.E2
+        # the prior belongs to the engine like the graph: a new engine over a model of the same shape takes it over
+        if self._prior is not None and self._prior.shape == (self.N, self.Q):
+            check(self._lib.sbmbp_set_vertex_prior(self._h, _dp(self._prior)))
+        else:
+            self._prior = None
 
     def init_messages(self, blockmodel, bp_messages_init_flag, conf, true_conf, seed):
         """belief_propagation.cpp:101-217"""
@@ -271,6 +287,32 @@ class BeliefPropagation:
     def set_nonedge_mode(self, mode=0, series_order=0):
         check(self._lib.sbmbp_set_nonedge_mode(self._h, mode, series_order))
 
+    def set_vertex_prior(self, prior):
+        """per-vertex label prior (sbmbp.h sbmbp_set_vertex_prior): an (N, Q) array of weights >= 0 with a positive one in
+        every row, stored as given; row i is updated with eta_q * prior[i, q] in place of eta_q. None removes the prior.
+        Single engine, Q <= 16, synchronous sweep order; while set, the engine runs the message-gather form only"""
+        if prior is None:
+            check(self._lib.sbmbp_set_vertex_prior(self._h, None))
+            self._prior = None
+            return
+        pr = np.array(prior, dtype=np.float64, order="C")
+        if not self._h:  # no engine yet (init_messages allocates it): the library says so
+            check(self._lib.sbmbp_set_vertex_prior(None, _dp(pr)))
+        if pr.shape != (self.N, self.Q):
+            raise ValueError("prior needs shape (N, Q)")
+        check(self._lib.sbmbp_set_vertex_prior(self._h, _dp(pr)))
+        self._prior = pr
+
+    def vertex_prior(self):
+        """the (N, Q) prior table the engine holds, or None"""
+        present = C.c_int(0)
+        check(self._lib.sbmbp_get_vertex_prior(self._h, None, C.byref(present)))
+        if not present.value:
+            return None
+        pr = np.zeros((self.N, self.Q))
+        check(self._lib.sbmbp_get_vertex_prior(self._h, _dp(pr), C.byref(present)))
+        return pr
+
     # -- hot path ---------------------------------------------------------------------------
     def converge(self, conv_crit, time_conv, dumping_rate):
         """belief_propagation.cpp:386-415; returns (niter, last max|delta|)"""
@@ -311,8 +353,8 @@ class BeliefPropagation:
         return Cm
 
     def em_expectations(self, cab=True):
-        """compute_na_expect + compute_cab_expect (belief_propagation.cpp:428-440, 892-989); cab=False: the group sizes only
-        (above Q = 16 the cab expectations, i.e. -m learn, are not implemented)"""
+        """compute_na_expect + compute_cab_expect (belief_propagation.cpp:428-440, 892-989), for every Q the engine takes;
+        cab=False: the group sizes only (cab_expect comes back as zeros)"""
         na, nna, cabe = np.zeros(self.Q), np.zeros(self.Q), np.zeros((self.Q, self.Q))
         check(self._lib.sbmbp_em_expectations(self._h, _dp(na), _dp(nna), _dp(cabe) if cab else None))
         return na, nna, cabe

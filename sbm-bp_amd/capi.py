@@ -91,6 +91,9 @@ SYMBOLS = {
     "sbmbp_set_state": (C.c_int, [C.c_void_p, c_dp, c_dp]),
     "sbmbp_get_state": (C.c_int, [C.c_void_p, c_dp, c_dp]),
     "sbmbp_get_field": (C.c_int, [C.c_void_p, c_dp]),
+    "sbmbp_set_vertex_prior": (C.c_int, [C.c_void_p, c_dp]),
+    "sbmbp_get_vertex_prior": (C.c_int, [C.c_void_p, c_dp, C.POINTER(C.c_int)]),
+    "sbmbp_prior_load": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, c_dp, c_u64p]),
     "sbmbp_set_schedule": (C.c_int, [C.c_void_p, C.c_double, C.c_uint32]),
     "sbmbp_set_gather_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "sbmbp_set_auto_relax": (C.c_int, [C.c_void_p, C.c_int]),

@@ -8,7 +8,8 @@
 // the line printed is the run of lowest free energy), --learn_restarts R (-m learn: R EM runs from seeds d .. d + R - 1 as one
 // replica batch, sbmbp_batch_learning; the two lines printed are those of the best run), and --gpus N: the graph is sharded by vertex range over N GPUs of
 // this node, one host thread per GPU driving the C++ multi-GPU driver (sbmbp_dist_*, RCCL over xGMI); with fewer devices
-// than ranks the ranks share devices over the in-process transport (a rehearsal, not a speed-up).
+// than ranks the ranks share devices over the in-process transport (a rehearsal, not a speed-up). --prior_path FILE: per-vertex
+// label priors (sbmbp_set_vertex_prior; single GPU, jacobi, up to 16 blocks), -m infer and -m learn.
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -42,7 +43,7 @@ const opt_spec OPTS[] = {
     // extensions
     {"precision", 0, 1}, {"device", 0, 1}, {"gather", 0, 1}, {"field_mix", 0, 1}, {"check_every", 0, 1}, {"metrics_json", 0, 1},
     {"gpus", 0, 1}, {"transport", 0, 1}, {"schedule", 0, 1}, {"step_fraction", 0, 1}, {"restarts", 0, 1},
-    {"learn_restarts", 0, 1},
+    {"learn_restarts", 0, 1}, {"prior_path", 0, 1},
 };
 
 const opt_spec *find_long(const std::string &name) {
@@ -167,7 +168,11 @@ void usage(const char *argv0) {
                  "                        output is that of the run with the lowest free energy (single GPU, jacobi, up to 16 blocks)\n"
                  "  --learn_restarts arg (=1)  -m learn: this many EM runs from seeds d, d+1, ... with the command line's initial parameters,\n"
                  "                        advanced together as one replica batch; the output is that of the best run: lowest free energy\n"
-                 "                        among the runs that stopped on fdiff < learning_conv_crit (single GPU, jacobi, up to 16 blocks)\n";
+                 "                        among the runs that stopped on fdiff < learning_conv_crit (single GPU, jacobi, up to 16 blocks)\n"
+                 "  --prior_path arg      per-vertex label priors: text, one line 'vertex w_0 ... w_{Q-1}' per annotated vertex, any order,\n"
+                 "                        weights >= 0 with a positive one per line; vertices not listed have no prior. A vertex's weights\n"
+                 "                        multiply the group prior in its marginal and its messages (-m infer and -m learn; single GPU,\n"
+                 "                        jacobi, up to 16 blocks)\n";
 }
 
 bool read_column(const std::string &path, std::vector<long long> &out) {  // load_beliefs/load_confs (graph_utilities.cpp:8-40)
@@ -366,6 +371,23 @@ int main(int argc, char const *argv[]) {
         else if (schedule == "coloured") conflict = "--learn_restarts cannot be combined with --schedule coloured (a replica batch sweeps synchronously)";
         else if (Q > 16) conflict = "--learn_restarts cannot be combined with more than 16 blocks (Q > 16)";
         if (conflict) { std::clog << "bp: " << conflict << "\n"; return 1; }
+    }
+    // per-vertex priors (sbmbp_set_vertex_prior): what they cannot be combined with, then the file, both before any device work
+    std::vector<double> prior;
+    uint64_t prior_rows = 0;
+    if (var_map.count("prior_path")) {
+        const char *conflict = nullptr;
+        if (n_gpus > 1) conflict = "--prior_path cannot be combined with --gpus above 1 (the multi-GPU driver takes no prior)";
+        else if (restarts > 1) conflict = "--prior_path cannot be combined with --restarts above 1 (a replica batch takes no prior)";
+        else if (lrestarts > 1) conflict = "--prior_path cannot be combined with --learn_restarts above 1 (a replica batch takes no prior)";
+        else if (schedule == "coloured") conflict = "--prior_path cannot be combined with --schedule coloured (the coloured order takes no prior)";
+        else if (Q > 16) conflict = "--prior_path cannot be combined with more than 16 blocks (Q > 16)";
+        if (conflict) { std::clog << "bp: " << conflict << "\n"; return 1; }
+        prior.resize(size_t(N) * Q);
+        if ((rc = sbmbp_prior_load(var_map.get("prior_path")[0].c_str(), N, Q, prior.data(), &prior_rows)) != SBMBP_OK) {
+            std::clog << "bp: --prior_path: " << sbmbp_strerror(rc) << ": " << sbmbp_last_error() << "\n";
+            return 1;
+        }
     }
     if (restarts > 1) {
         // ---- replica batch: R runs of -m infer over the one graph, seeds d .. d + R - 1 (include/sbmbp.h, "Replica batches") ----
@@ -646,6 +668,7 @@ int main(int argc, char const *argv[]) {
     if ((rc = sbmbp_set_schedule(eng, num("field_mix", 1.0), unsigned(num("check_every", 8)))) != SBMBP_OK) return fail(rc);
     if (var_map.count("gather") && var_map.get("gather")[0] == "messages") sbmbp_set_gather_mode(eng, 1);
     if (schedule == "coloured" && (rc = sbmbp_set_sweep_order(eng, 1, nullptr, num("step_fraction", 0.0))) != SBMBP_OK) return fail(rc);
+    if (!prior.empty() && (rc = sbmbp_set_vertex_prior(eng, prior.data())) != SBMBP_OK) return fail(rc);
     stage("sweep order");
 
     const auto t0 = std::chrono::steady_clock::now();
@@ -698,7 +721,9 @@ int main(int argc, char const *argv[]) {
            << ",\"marginal_gather_sweeps\":" << st.psi_form_sweeps << ",\"run_seconds\":" << secs
            << ",\"bytes_per_sweep\":" << st.bytes_per_sweep << ",\"device_bytes\":" << st.device_bytes
            << ",\"relaxation\":[" << ar_f << "," << ar_g << "," << ar_mix << "," << ar_damp << "]"
-           << ",\"schedule\":\"" << (order == 1 ? "coloured" : "jacobi") << "\",\"colours\":" << n_colours << ",\"steps\":" << n_steps << "}\n";
+           << ",\"schedule\":\"" << (order == 1 ? "coloured" : "jacobi") << "\",\"colours\":" << n_colours << ",\"steps\":" << n_steps;
+        if (var_map.count("prior_path")) mj << ",\"prior_rows\":" << prior_rows;
+        mj << "}\n";
     }
     sbmbp_destroy(eng);
     sbmbp_graph_destroy(graph);

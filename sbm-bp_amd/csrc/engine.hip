@@ -73,6 +73,7 @@ struct sbmbp_engine {
     std::vector<uint32_t> h_hub_frag0;  // [n_hub + 1]
     uint32_t *d_fold_counters = nullptr;  // arrival counter of k_fold_finalize (zero between launches)
     int32_t *d_clamp = nullptr;
+    double *d_prior = nullptr;     // per-vertex prior [N*Q] (sbmbp_set_vertex_prior), or null: none. Belongs to the engine like the graph
     uint32_t n_blk = 0, n_hub = 0;
     // state in HBM
     double *d_M[2] = {nullptr, nullptr};
@@ -394,7 +395,7 @@ int launch_hub_msg(sbmbp_engine *e, hipStream_t st, const double *Mold, double *
     }
     DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_frag_cavity_msg<QQ>), dim3(nf), dim3(BLOCK), 0, st, e->d_row_ptr, Mold, Mnew, psi_old, psi_new,
                                         e->d_hub_row, e->d_hub_blk, hf, 0u, e->d_P, int(e->dc != 0), damp,
-                                        e->d_partials, clamp));
+                                        e->d_partials, clamp, e->d_prior));
     return SBMBP_OK;
 }
 
@@ -480,6 +481,16 @@ int launch_sweep(sbmbp_engine *e, uint32_t j, double damp, bool psi_form, bool f
                                                 Mnew, psi_old, psi_new, e->d_blk_row, e->d_blk_e0, e->d_P, int(e->dc), e->d_partials,
                                                 (const int32_t *)nullptr, shard_io{}, e->n_blk, SBMBP_XCD_REMAP,
                                                 Mold, int(first_from_psi)));
+        }
+    } else if (e->d_prior != nullptr) {  // a per-vertex prior is set: the prior twin of k_sweep
+        if (e->dc == 2) {
+            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_prior<QQ, true>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
+                                                e->d_rev, e->d_nbr, e->d_deg, Mold, Mnew, psi_old, psi_new, clamp, e->d_blk_row, e->d_blk_e0, e->d_P,
+                                                1, damp, e->d_partials, e->d_prior));
+        } else {
+            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_prior<QQ, false>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
+                                                e->d_rev, e->d_nbr, e->d_deg, Mold, Mnew, psi_old, psi_new, clamp, e->d_blk_row, e->d_blk_e0, e->d_P,
+                                                int(e->dc), damp, e->d_partials, e->d_prior));
         }
     } else if (e->dc == 2) {
         DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep<QQ, true>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
@@ -575,7 +586,10 @@ int message_diff(sbmbp_engine *e, double *out) {
 }
 
 bool psi_form_allowed(const sbmbp_engine *e, double damping) {
-    return !e->wide && e->gather_mode == 0 && damping == 1.0 && (!e->has_clamp || e->clamp_onehot) && e->dc != 2 && e->w_positive && e->E2 > 0;
+    // (under a per-vertex prior the marginal-gather form would still be exact - psi_l carries the prior - but its kernels do not
+    // take one: DESIGN.md section 9)
+    return !e->wide && e->gather_mode == 0 && damping == 1.0 && (!e->has_clamp || e->clamp_onehot) && e->dc != 2 && e->w_positive && e->E2 > 0 &&
+           e->d_prior == nullptr;
 }
 
 void free_coloured(sbmbp_engine *e) {
@@ -929,7 +943,25 @@ int site_edge_terms(sbmbp_engine *e, bool want_entropy, double out[4], double *d
     CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (FE_NP + 1)));
     const double *M = e->d_M[e->cur];
     const double *Min = (e->sharded && e->incoming_src == 0) ? e->d_Min : nullptr;
-    if (e->dc == 2) {
+    if (e->d_prior != nullptr) {  // a per-vertex prior is set: the prior twins, whose site products take the row's prior line
+        if (e->dc == 2) {
+            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_fe_frame_prior<QQ, true>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
+                                                e->d_rev, e->d_nbr, e->d_deg, M, Min, e->d_blk_row, e->d_blk_e0, e->d_P, 1, int(want_entropy), e->d_partials,
+                                                e->d_prior));
+            if (e->n_hub)
+                DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_fe_hub_prior<QQ, true>), dim3(e->n_hub), dim3(BLOCK), 0, e->stream, e->d_row_ptr,
+                                                    e->d_rev, e->d_nbr, e->d_deg, M, Min, e->d_hub_row, e->d_hub_blk, e->d_P, 1,
+                                                    int(want_entropy), e->d_partials, uint32_t(FE_NP + 1), 0xffffffffu, e->d_prior));
+        } else {
+            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_fe_frame_prior<QQ, false>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
+                                                e->d_rev, e->d_nbr, e->d_deg, M, Min, e->d_blk_row, e->d_blk_e0, e->d_P, int(e->dc), int(want_entropy),
+                                                e->d_partials, e->d_prior));
+            if (e->n_hub)
+                DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_fe_hub_prior<QQ, false>), dim3(e->n_hub), dim3(BLOCK), 0, e->stream, e->d_row_ptr,
+                                                    e->d_rev, e->d_nbr, e->d_deg, M, Min, e->d_hub_row, e->d_hub_blk, e->d_P, int(e->dc),
+                                                    int(want_entropy), e->d_partials, uint32_t(FE_NP + 1), 0xffffffffu, e->d_prior));
+        }
+    } else if (e->dc == 2) {
         DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_fe_frame<QQ, true>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
                                             e->d_rev, e->d_nbr, e->d_deg, M, Min, e->d_blk_row, e->d_blk_e0, e->d_P, 1, int(want_entropy), e->d_partials));
         if (e->n_hub)
@@ -1281,7 +1313,7 @@ void sbmbp_destroy(sbmbp_engine_t *e) {
     if (e->ext_psi) e->d_psi[0] = e->d_psi[1] = nullptr;  // caller-owned
     void *ptrs[] = {e->d_deg, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_src, e->d_blk_row, e->d_blk_e0, e->d_hub_row, e->d_hub_blk, e->d_true,
                     e->d_clamp, e->d_M[0], e->d_M[1], e->d_psi[0], e->d_psi[1], e->d_Min, e->d_snd_ptr, e->d_snd_slot, e->d_P, e->d_partials, e->d_small, e->d_hist, e->d_mats,
-                    e->d_stage, e->d_frag_hub, e->d_hub_frag0, e->d_hub_b, e->d_hub_pA, e->d_hub_pE, e->d_fold_counters, e->d_Pw};
+                    e->d_stage, e->d_frag_hub, e->d_hub_frag0, e->d_hub_b, e->d_hub_pA, e->d_hub_pE, e->d_fold_counters, e->d_Pw, e->d_prior};
     for (void *p : ptrs) if (p) hipFree(p);
     free_coloured(e);
     for (auto ev : e->ev) hipEventDestroy(ev);
@@ -1505,6 +1537,62 @@ int sbmbp_set_state(sbmbp_engine_t *e, const double *psi, const double *msg_out)
     e->clamp_onehot = false;  // an arbitrary state: clamped rows need the general (message-gather) sweep
     return SBMBP_OK;
 }
+
+// ---- per-vertex prior ------------------------------------------------------------------------------
+// first row of an N x Q table that is no prior line (a negative, NaN or Inf entry, or no positive one), or N
+static uint32_t first_bad_prior_row(const double *prior, uint32_t N, uint32_t Q, std::string *why) {
+    for (uint32_t i = 0; i < N; ++i) {
+        bool pos = false;
+        for (uint32_t q = 0; q < Q; ++q) {
+            const double w = prior[size_t(i) * Q + q];
+            if (!(w >= 0.0) || std::isinf(w)) { *why = "entry " + std::to_string(q) + " is negative, NaN or Inf"; return i; }
+            pos = pos || w > 0.0;
+        }
+        if (!pos) { *why = "no entry is positive"; return i; }
+    }
+    return N;
+}
+
+int sbmbp_set_vertex_prior(sbmbp_engine_t *e, const double *prior) {
+    device_scope dev_(e);
+    if (!e) return arg_error(__func__, __LINE__);
+    if (prior == nullptr) {  // remove
+        if (e->d_prior) {
+            HIPCHK(hipStreamSynchronize(e->stream));
+            (void)hipFree(e->d_prior);
+            e->d_prior = nullptr;
+            e->device_bytes -= size_t(e->N) * e->Q * 8;
+            e->psi_consistent = false; e->fz.valid = false;
+        }
+        return SBMBP_OK;
+    }
+    if (e->wide) { set_error("a per-vertex prior is implemented up to Q = 16 (the lane-per-edge kernels); Q = " + std::to_string(e->Q)); return SBMBP_ERR_UNSUPPORTED; }
+    if (e->sharded) { set_error("a per-vertex prior runs on the single engine only: a shard engine takes none"); return SBMBP_ERR_UNSUPPORTED; }
+    if (e->sweep_order == 1) { set_error("a per-vertex prior cannot be combined with the coloured sweep order: sbmbp_set_sweep_order(e, 0, ...) first"); return SBMBP_ERR_UNSUPPORTED; }
+    std::string why;
+    const uint32_t bad = first_bad_prior_row(prior, e->N, e->Q, &why);
+    if (bad < e->N) { set_error("sbmbp_set_vertex_prior: prior row of vertex " + std::to_string(bad) + ": " + why); return SBMBP_ERR_ARG; }
+    if (!e->d_prior) CHK(dev_alloc(e, &e->d_prior, size_t(e->N) * e->Q));
+    HIPCHK(hipMemcpyAsync(e->d_prior, prior, size_t(e->N) * e->Q * 8, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->psi_consistent = false; e->fz.valid = false;
+    return SBMBP_OK;
+}
+int sbmbp_get_vertex_prior(sbmbp_engine_t *e, double *prior, int *present) {
+    device_scope dev_(e);
+    if (!e) return arg_error(__func__, __LINE__);
+    if (present) *present = e->d_prior ? 1 : 0;
+    if (prior && e->d_prior) {
+        HIPCHK(hipMemcpyAsync(prior, e->d_prior, size_t(e->N) * e->Q * 8, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    return SBMBP_OK;
+}
+int sbmbp_prior_load(const char *path, uint32_t n_vertices, uint32_t Q, double *prior, uint64_t *n_rows_given) {
+    if (!path || !prior || Q < 1) return arg_error(__func__, __LINE__);
+    return read_prior_table(path, n_vertices, Q, prior, n_rows_given);
+}
+
 int sbmbp_get_state(sbmbp_engine_t *e, double *psi, double *msg_out) {
     device_scope dev_(e);
     if (!e) return arg_error(__func__, __LINE__);
@@ -1586,6 +1674,7 @@ int sbmbp_set_sweep_order(sbmbp_engine_t *e, int order, const uint32_t *colour, 
     if (order == 0) { e->sweep_order = 0; return SBMBP_OK; }
     if (e->sharded) { set_error("the coloured sweep order runs on the single engine only: a shard engine sweeps synchronously"); return SBMBP_ERR_UNSUPPORTED; }
     if (e->wide) { set_error("the coloured sweep order is implemented up to Q = 16"); return SBMBP_ERR_UNSUPPORTED; }
+    if (e->d_prior) { set_error("the coloured sweep order takes no per-vertex prior: remove it first (sbmbp_set_vertex_prior(e, NULL))"); return SBMBP_ERR_UNSUPPORTED; }
     // the engine keeps the row offsets on the host; the neighbour lists come back from the device (first use only)
     std::vector<uint64_t> rp(e->h_row_ptr.begin(), e->h_row_ptr.end());
     std::vector<uint32_t> nbr(e->E2);
@@ -1742,6 +1831,7 @@ int sbmbp_get_stats(sbmbp_engine_t *e, sbmbp_stats *out) {
     out->sweep_launches = e->sweep_launches;
     // B_sweep = E2 (3*8Q + 4) + N (8Q + 8): SURVEY 8(d); dc 2 adds the neighbour index (4 B/edge)
     out->bytes_per_sweep = double(e->E2) * (24.0 * e->Q + 4.0 + (e->dc == 2 ? 4.0 : 0.0)) + double(e->N) * (8.0 * e->Q + 8.0);
+    if (e->d_prior) out->bytes_per_sweep += 8.0 * e->Q * double(e->N);  // every row reads its prior line once
     out->device_bytes = e->device_bytes;
     out->n_blocks = e->n_blk;
     out->n_hub_rows = e->n_hub;

@@ -16,8 +16,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <memory>
 #include <random>
+#include <sstream>
+#include <string>
 #include <thread>
 
 #include "../../include/sbmbp.h"
@@ -302,6 +305,44 @@ int read_int_column(const char *path, std::vector<int64_t> &values) {
         values.push_back(v);
     }
     std::fclose(f);
+    return SBMBP_OK;
+}
+
+int read_prior_table(const char *path, uint32_t n, uint32_t Q, double *prior, uint64_t *n_rows_given) {
+    std::ifstream f(path);
+    if (!f.is_open()) { set_error(std::string("cannot open file: ") + path); return SBMBP_ERR_IO; }
+    for (size_t k = 0; k < size_t(n) * Q; ++k) prior[k] = 1.0;
+    std::vector<char> seen(n, 0);
+    uint64_t given = 0, lineno = 0;
+    std::string line;
+    auto bad = [&](const std::string &what) {
+        set_error(std::string(path) + " line " + std::to_string(lineno) + ": " + what);
+        return SBMBP_ERR_ARG;
+    };
+    while (std::getline(f, line)) {
+        ++lineno;
+        std::vector<std::string> tok;
+        std::istringstream ls(line);
+        for (std::string t; ls >> t;) tok.push_back(t);
+        if (tok.empty()) continue;
+        char *end = nullptr;
+        const unsigned long long v = std::strtoull(tok[0].c_str(), &end, 10);
+        if (tok[0][0] == '-' || end == tok[0].c_str() || *end != '\0') return bad("vertex id '" + tok[0] + "' is not a non-negative integer");
+        if (v >= n) return bad("vertex id " + tok[0] + " >= N = " + std::to_string(n));
+        if (tok.size() != size_t(Q) + 1) return bad(std::to_string(tok.size() - 1) + " weights where Q = " + std::to_string(Q) + " are needed");
+        if (seen[v]) return bad("vertex " + tok[0] + " is named twice");
+        bool pos = false;
+        for (uint32_t q = 0; q < Q; ++q) {
+            const double w = std::strtod(tok[q + 1].c_str(), &end);
+            if (end == tok[q + 1].c_str() || *end != '\0' || !(w >= 0.0) || std::isinf(w)) return bad("bad value '" + tok[q + 1] + "' (a finite number >= 0 is needed)");
+            prior[size_t(v) * Q + q] = w;
+            pos = pos || w > 0.0;
+        }
+        if (!pos) return bad("bad value: vertex " + tok[0] + " has no positive weight");
+        seen[v] = 1;
+        ++given;
+    }
+    if (n_rows_given) *n_rows_given = given;
     return SBMBP_OK;
 }
 

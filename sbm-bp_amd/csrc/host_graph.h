@@ -29,6 +29,10 @@ int graph_from_csr(sbmbp_graph &g, uint32_t n, uint64_t e2, const uint64_t *row_
                    const uint32_t *rev);
 int read_edgelist(const char *path, std::vector<uint32_t> &pairs);
 int read_int_column(const char *path, std::vector<int64_t> &values);  // load_beliefs/load_confs format
+// per-vertex prior file (sbmbp_prior_load): one line "vertex w_0 .. w_{Q-1}" per annotated vertex, any order; prior[n*Q] is
+// filled with ones where no line names the vertex. SBMBP_ERR_IO: unreadable; SBMBP_ERR_ARG with the line number: id >= n, a
+// vertex named twice, a wrong column count, a value that is no finite number >= 0, a line without a positive weight
+int read_prior_table(const char *path, uint32_t n, uint32_t Q, double *prior, uint64_t *n_rows_given);
 
 void param_from_epsilon_c(uint32_t N, uint32_t Q, double epsilon, double c, double *cab, uint32_t *na);
 void param_from_direct(uint32_t N, uint32_t Q, const double *pa, const double *cab_upper, double *cab, uint32_t *na);

@@ -414,6 +414,15 @@ template <int Q> __device__ __forceinline__ void x_norm(double (&A)[Q], int (&ae
         ae[q] += k;
     }
 }
+// one more factor of a product with per-component exponents: the prior line pl[Q] of a row (sbmbp_set_vertex_prior). A zero
+// entry stays an exact zero with exponent 0, which the log-domain paths below turn into exp(-inf) = 0.
+template <int Q> __device__ __forceinline__ void prior_factor(const double *__restrict__ pl, double (&A)[Q], int (&ae)[Q]) {
+    double w[Q];
+    load_vec<Q>(pl, w);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) A[q] *= w[q];
+    x_norm<Q>(A, ae);
+}
 // psi~[q] = A[q] 2^ae[q] eta[q] F_i[q], returned relative to its largest component (in A); the return value is the
 // sum of the returned components and *lmax the log of the factor taken out (log_partition = *lmax + log(sum))
 template <int Q>
@@ -602,12 +611,44 @@ k_sweep(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ rev, 
 #define SWEEP_PSI
 #define SWEEP_MNEW
 #define SWEEP_RECORD partials + size_t(blockIdx.x) * (Q + 1)
+#define SWEEP_ROW_START(r, v) _Pragma("unroll") for (int q = 0; q < Q; ++q) v[q] = 1.0;
+#define SWEEP_ROW_FACTOR(r, v, x)
 #include "sweep_msg_body.inc"
 #undef SWEEP_REPLICA
 #undef SWEEP_MOLD
 #undef SWEEP_PSI
 #undef SWEEP_MNEW
 #undef SWEEP_RECORD
+#undef SWEEP_ROW_START
+#undef SWEEP_ROW_FACTOR
+}
+
+// K1v: k_sweep under a per-vertex prior (sbmbp_set_vertex_prior): row i's product starts from its prior line prior[i*Q ..]
+// instead of 1, so the prior is in the marginal, in every cavity A / b_e and in the exact cavity product, like the field of a
+// virtual incoming edge. The line is loaded into registers with the row's ftab line, ahead of the product loop; nothing of it
+// goes through LDS. Same body, other hooks: k_sweep itself is the code it was (tools/kernel_isa_diff.py).
+template <int Q, bool DC2>
+__global__ void __launch_bounds__(frame_cfg<Q>::TPB) __attribute__((amdgpu_waves_per_eu(sweep_waves<Q>::N)))
+k_sweep_prior(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ rev, const uint32_t *__restrict__ nbr, const uint32_t *__restrict__ ndeg /* degree of every table row (DC2 only) */,
+              const double *__restrict__ Mold, double *__restrict__ Mnew, const double *__restrict__ psi_old,
+              double *__restrict__ psi, const int32_t *__restrict__ clamp, const uint32_t *__restrict__ blk_row,
+              const uint32_t *__restrict__ blk_e0, const dev_params *__restrict__ P, int dc, double damp, double *__restrict__ partials,
+              const double *__restrict__ prior /* [N*Q], entries >= 0, a positive one in every row */) {
+#define SWEEP_REPLICA
+#define SWEEP_MOLD
+#define SWEEP_PSI
+#define SWEEP_MNEW
+#define SWEEP_RECORD partials + size_t(blockIdx.x) * (Q + 1)
+#define SWEEP_ROW_START(r, v) load_vec<Q>(prior + size_t(r0 + uint32_t(r)) * Q, v);
+#define SWEEP_ROW_FACTOR(r, v, x) { prior_factor<Q>(prior + size_t(r0 + uint32_t(r)) * Q, v, x); }
+#include "sweep_msg_body.inc"
+#undef SWEEP_REPLICA
+#undef SWEEP_MOLD
+#undef SWEEP_PSI
+#undef SWEEP_MNEW
+#undef SWEEP_RECORD
+#undef SWEEP_ROW_START
+#undef SWEEP_ROW_FACTOR
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1422,7 +1463,8 @@ __global__ void __launch_bounds__(BLOCK)
 k_hub_frag_cavity_msg(const uint32_t *__restrict__ row_ptr, const double *__restrict__ Mold, double *__restrict__ Mnew,
                       const double *__restrict__ psi_old, double *__restrict__ psi, const uint32_t *__restrict__ hub_row,
                       const uint32_t *__restrict__ hub_blk, hub_frags hf, uint32_t frag_first, const dev_params *__restrict__ P, int dc,
-                      double damp, double *__restrict__ partials, const int32_t *__restrict__ clamp) {
+                      double damp, double *__restrict__ partials, const int32_t *__restrict__ clamp,
+                      const double *__restrict__ prior /* per-vertex prior [N*Q] (k_sweep_prior), or null */) {
     if (P->stop) return;
     __shared__ double sAw[(BLOCK / 64) * Q];
     __shared__ int sEw[(BLOCK / 64) * Q];
@@ -1459,6 +1501,7 @@ k_hub_frag_cavity_msg(const uint32_t *__restrict__ row_ptr, const double *__rest
         x_norm<Q>(A, ae);
     }
     block_product_shfl<Q, BLOCK / 64>(A, ae, sAw, sEw);
+    if (prior != nullptr) prior_factor<Q>(prior + size_t(i) * Q, A, ae);  // uniform: one line per workgroup, before the exponents are normalised
     const double tot = apply_field_x<Q>(P, dc, di, A, ae);
     const double inv = 1.0 / tot;
     if (f == f0 && tid == 0) {
@@ -1652,110 +1695,21 @@ k_fe_frame(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ re
            const double *__restrict__ M, const double *__restrict__ Min /* incoming messages in edge order, or null: gather M[rev] */,
            const uint32_t *__restrict__ blk_row, const uint32_t *__restrict__ blk_e0, const dev_params *__restrict__ P,
            int dc, int want_entropy, double *__restrict__ partials) {
-    constexpr int EPT = frame_cfg<Q>::EPT, CAP = frame_cfg<Q>::CAP, RCAP = frame_cfg<Q>::RCAP;
-    __shared__ double sb[CAP * Q];
-    __shared__ double sc[CAP * Q];  // entropy: b with plain cab weights (no beta)
-    __shared__ uint32_t srp[RCAP + 1];
-    __shared__ uint16_t srow[CAP];
-    __shared__ double sred[frame_cfg<Q>::WAVES * (FE_NP + 1)];
-    const int tid = threadIdx.x;
-    // as in the sweep kernels: segment bounds from one level of scalar loads, then every load of the lane-per-edge phase is
-    // issued branch-free and back to back (reverse index, own record, row offsets, then the gathers) before anything waits
-    const uint32_t r0 = blk_row[blockIdx.x], r1 = blk_row[blockIdx.x + 1];
-    const int nrows = int(r1 - r0);
-    const uint32_t e0 = blk_e0[blockIdx.x];
-    const int ne = int(blk_e0[blockIdx.x + 1] - e0);
-    double acc[FE_NP] = {0.0, 0.0, 0.0, 0.0};
-    if (ne <= CAP) {
-        constexpr int RPT = RCAP / frame_cfg<Q>::TPB + 1;
-        uint32_t kk[EPT], rk[EPT], rpv[RPT];
-        double mo_[EPT][Q], mi_[EPT][Q];
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) {
-            const int le = j * frame_cfg<Q>::TPB + tid;
-            kk[j] = (ne > 0) ? e0 + uint32_t(le < ne ? le : 0) : 0u;
-        }
-        if (Min == nullptr) {  // uniform
-#pragma unroll
-            for (int j = 0; j < EPT; ++j) rk[j] = rev[kk[j]];
-        }
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) load_msg<Q>(M, size_t(kk[j]), mo_[j]);
-#pragma unroll
-        for (int t = 0; t < RPT; ++t) { const int r = tid + t * frame_cfg<Q>::TPB; rpv[t] = row_ptr[r0 + uint32_t(r < nrows ? r : nrows)]; }
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) load_msg<Q>(Min ? Min : M, Min ? size_t(kk[j]) : size_t(rk[j]), mi_[j]);
-#pragma unroll
-        for (int t = 0; t < RPT; ++t) { const int r = tid + t * frame_cfg<Q>::TPB; if (r <= nrows) srp[r] = rpv[t] - e0; }
-        __syncthreads();
-        if (DC2) {  // per-edge weights need the edge -> row map
-            for (int r = tid; r < nrows; r += frame_cfg<Q>::TPB)
-                for (int e = int(srp[r]); e < int(srp[r + 1]); ++e) srow[e] = uint16_t(r);
-            __syncthreads();
-        }
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) {
-            const int le = j * frame_cfg<Q>::TPB + tid;
-            if (le < ne) {
-                double (&mi)[Q] = mi_[j];
-                double (&mo)[Q] = mo_[j];
-                double b[Q];
-                double didl = 0.0;
-                if (DC2) {
-                    const int r = srow[le];
-                    const uint32_t l = nbr[e0 + le];
-                    didl = double(srp[r + 1] - srp[r]) * double(ndeg[l]);
-                }
-                edge_field<Q, DC2>(P, mi, didl, b);
-                store_vec<Q>(&sb[le * Q], b);
-                if (want_entropy) {
-                    double c[Q];
-#pragma unroll
-                    for (int q = 0; q < Q; ++q) {
-                        double a = 0.0;
-#pragma unroll
-                        for (int t = 0; t < Q; ++t) a += P->cab[t * Q + q] * mi[t];
-                        c[q] = a;
-                    }
-                    store_vec<Q>(&sc[le * Q], c);
-                }
-                double ln, en;
-                edge_terms<Q, DC2>(P, mi, mo, didl, want_entropy, ln, en);
-                acc[1] += ln;
-                if (want_entropy) acc[3] += en;
-            }
-        }
-        __syncthreads();
-        for (int r = tid; r < nrows; r += frame_cfg<Q>::TPB) {
-            const int es = int(srp[r]), ee = int(srp[r + 1]);
-            const double di = double(ee - es);
-            double A[Q];
-            int ae[Q];
-#pragma unroll
-            for (int q = 0; q < Q; ++q) { A[q] = 1.0; ae[q] = 0; }
-            for (int e = es; e < ee; ++e) {
-#pragma unroll
-                for (int q = 0; q < Q; ++q) A[q] *= sb[e * Q + q];
-                if (((e - es) & 7) == 7) x_norm<Q>(A, ae);  // eight factors of O(W) stay far inside the double range
-            }
-            x_norm<Q>(A, ae);
-            acc[0] += log_partition_x<Q>(P, dc, di, A, ae);  // log Z_i  (bp.cpp:446-502)
-            if (want_entropy) {  // e_site (bp.cpp:506-560): no beta, weights exp(a + log eta - h/N)
-                double C[Q];
-                int ce[Q];
-#pragma unroll
-                for (int q = 0; q < Q; ++q) { C[q] = 1.0; ce[q] = 0; }
-                for (int e = es; e < ee; ++e) {
-#pragma unroll
-                    for (int q = 0; q < Q; ++q) C[q] *= sc[e * Q + q];
-                    if (((e - es) & 7) == 7) x_norm<Q>(C, ce);
-                }
-                x_norm<Q>(C, ce);
-                acc[2] += entropy_site_x<Q>(P, C, ce);
-            }
-        }
-    }
-    block_reduce_store<FE_NP, frame_cfg<Q>::WAVES>(acc, 0.0, sred, partials + size_t(blockIdx.x) * (FE_NP + 1));
+#define FE_SITE_FACTOR(i, v, x)
+#include "fe_frame_body.inc"
+#undef FE_SITE_FACTOR
+}
+// k_fe_frame under a per-vertex prior (sbmbp_set_vertex_prior): the prior line of a row is one more factor of both site products
+template <int Q, bool DC2>
+__global__ void __launch_bounds__(frame_cfg<Q>::TPB)
+k_fe_frame_prior(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ rev, const uint32_t *__restrict__ nbr, const uint32_t *__restrict__ ndeg /* degree of every table row (DC2 only) */,
+           const double *__restrict__ M, const double *__restrict__ Min /* incoming messages in edge order, or null: gather M[rev] */,
+           const uint32_t *__restrict__ blk_row, const uint32_t *__restrict__ blk_e0, const dev_params *__restrict__ P,
+           int dc, int want_entropy, double *__restrict__ partials,
+           const double *__restrict__ prior /* [N*Q] */) {
+#define FE_SITE_FACTOR(i, v, x) prior_factor<Q>(prior + size_t(i) * Q, v, x);
+#include "fe_frame_body.inc"
+#undef FE_SITE_FACTOR
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1980,56 +1934,22 @@ k_fe_hub(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ rev,
          const uint32_t *__restrict__ hub_blk, const dev_params *__restrict__ P, int dc, int want_entropy,
          double *__restrict__ partials, uint32_t rec_stride /* doubles per record (>= FE_NP + 1) */,
          uint32_t rec_first /* record of hub 0, or 0xffffffff: the hub's own segment record hub_blk[h] */) {
-    __shared__ double sAq[BLOCK * Q];
-    __shared__ double sCq[BLOCK * Q];
-    __shared__ int sEq[BLOCK * Q];
-    __shared__ double sred[4 * (FE_NP + 1)];
-    const int tid = threadIdx.x;
-    const uint32_t i = hub_row[blockIdx.x];
-    const uint32_t e0 = row_ptr[i], d = row_ptr[i + 1] - e0;
-    const double di = double(d);
-    double acc[FE_NP] = {0.0, 0.0, 0.0, 0.0};
-    double A[Q], C[Q];
-    int ae[Q], ce[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) { A[q] = 1.0; C[q] = 1.0; ae[q] = 0; ce[q] = 0; }
-    for (uint32_t le = tid; le < d; le += BLOCK) {
-        double mi[Q], mo[Q], b[Q];
-        load_msg<Q>(Min ? Min : M, Min ? size_t(e0 + le) : size_t(rev[e0 + le]), mi);
-        load_msg<Q>(M, size_t(e0 + le), mo);
-        double didl = 0.0;
-        if (DC2) { const uint32_t l = nbr[e0 + le]; didl = di * double(ndeg[l]); }
-        edge_field<Q, DC2>(P, mi, didl, b);
-#pragma unroll
-        for (int q = 0; q < Q; ++q) A[q] *= b[q];
-        x_norm<Q>(A, ae);
-        if (want_entropy) {
-#pragma unroll
-            for (int q = 0; q < Q; ++q) {
-                double a = 0.0;
-#pragma unroll
-                for (int t = 0; t < Q; ++t) a += P->cab[t * Q + q] * mi[t];
-                C[q] *= a;
-            }
-            x_norm<Q>(C, ce);
-        }
-        double ln, en;
-        edge_terms<Q, DC2>(P, mi, mo, didl, want_entropy, ln, en);
-        acc[1] += ln;
-        if (want_entropy) acc[3] += en;
-    }
-    block_product_x<Q>(A, ae, sAq, sEq);
-    if (want_entropy) {  // uniform
-        __syncthreads();
-        block_product_x<Q>(C, ce, sCq, sEq);
-    }
-    if (tid == 0) {
-        acc[0] += log_partition_x<Q>(P, dc, di, A, ae);
-        if (want_entropy) acc[2] += entropy_site_x<Q>(P, C, ce);
-    }
-    double *rec = partials + size_t(rec_first == 0xffffffffu ? hub_blk[blockIdx.x] : rec_first + blockIdx.x) * rec_stride;
-    block_reduce_store<FE_NP>(acc, 0.0, sred, rec);
-    for (uint32_t x = FE_NP + 1 + tid; x < rec_stride; x += BLOCK) rec[x] = 0.0;  // the other columns of a wider record (k_fe_psi)
+#define FE_SITE_FACTOR(i, v, x)
+#include "fe_hub_body.inc"
+#undef FE_SITE_FACTOR
+}
+// k_fe_hub under a per-vertex prior (k_fe_frame_prior)
+template <int Q, bool DC2>
+__global__ void __launch_bounds__(BLOCK)
+k_fe_hub_prior(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ rev, const uint32_t *__restrict__ nbr, const uint32_t *__restrict__ ndeg /* degree of every table row (DC2 only) */,
+         const double *__restrict__ M, const double *__restrict__ Min, const uint32_t *__restrict__ hub_row,
+         const uint32_t *__restrict__ hub_blk, const dev_params *__restrict__ P, int dc, int want_entropy,
+         double *__restrict__ partials, uint32_t rec_stride /* doubles per record (>= FE_NP + 1) */,
+         uint32_t rec_first /* record of hub 0, or 0xffffffff: the hub's own segment record hub_blk[h] */,
+         const double *__restrict__ prior /* [N*Q] */) {
+#define FE_SITE_FACTOR(i, v, x) prior_factor<Q>(prior + size_t(i) * Q, v, x);
+#include "fe_hub_body.inc"
+#undef FE_SITE_FACTOR
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -60,12 +60,16 @@ k_sweep_batch(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__
     double *__restrict__ psi = psi_all + (size_t(mc ^ 1) * R + rep) * psi_stride;
 #define SWEEP_MNEW double *__restrict__ Mnew = Mall + (size_t(mc ^ 1) * R + rep) * msg_stride;
 #define SWEEP_RECORD rec_all + size_t(rep) * rec_stride + size_t(blockIdx.x) * (Q + 1)
+#define SWEEP_ROW_START(r, v) _Pragma("unroll") for (int q = 0; q < Q; ++q) v[q] = 1.0;
+#define SWEEP_ROW_FACTOR(r, v, x)
 #include "sweep_msg_body.inc"
 #undef SWEEP_REPLICA
 #undef SWEEP_MOLD
 #undef SWEEP_PSI
 #undef SWEEP_MNEW
 #undef SWEEP_RECORD
+#undef SWEEP_ROW_START
+#undef SWEEP_ROW_FACTOR
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// The body of the synchronous message-gather sweep: THE definition of k_sweep (kernels.h) and k_sweep_batch
+// The body of the synchronous message-gather sweep: THE definition of k_sweep, k_sweep_prior (kernels.h) and k_sweep_batch
 // (kernels_batch.h), which include this file between their braces. Not a header: no guard, no namespace, and it reads the
 // kernel's parameters by name:
 //     row_ptr rev nbr ndeg clamp blk_row blk_e0 dc damp          both kernels
@@ -10,6 +10,11 @@
 //     SWEEP_PSI       before phase 2: psi_old, psi
 //     SWEEP_MNEW      before phase 3: Mnew
 //     SWEEP_RECORD    an expression: where the segment's (Q + 1)-record goes
+//     SWEEP_ROW_START(r, v)       phase 2, lane per row: v[Q] = the factor the product of row r starts from (all ones; the
+//                                 row's prior line in k_sweep_prior), issued with the ftab line before the product loop
+//     SWEEP_ROW_FACTOR(r, v, x)   behind a product with per-component exponents (the wave product of a row above BIG_ROW,
+//                                 the exact cavity of phase 3): one more factor into (v, x) before apply_field_x normalises
+//                                 the exponents (nothing; the row's prior line in k_sweep_prior)
 // It is a textual include and not a __device__ function because the function form, inlined, is other code for this
 // compiler in every instantiation (DESIGN.md section 8 has the register counts; tools/kernel_isa_diff.py compares builds).
     constexpr int EPT = frame_cfg<Q>::EPT, CAP = frame_cfg<Q>::CAP, RCAP = frame_cfg<Q>::RCAP;
@@ -118,8 +123,7 @@
             double A[Q], ft[Q];
             const bool tab = dc != 0 && ee - es <= FT_D;  // the field factors of this degree: loaded while the product runs
             if (tab) load_vec<Q>(P->ftab + size_t(ee - es) * QMAX, ft);
-#pragma unroll
-            for (int q = 0; q < Q; ++q) A[q] = 1.0;
+            SWEEP_ROW_START(r, A)
             for (int e = es; e < ee; ++e) {
                 double b[Q];
                 load_vec<Q>(&sb[e * Q], b);
@@ -137,7 +141,10 @@
             double A[Q];
             int ae[Q];
             row_product_wave<Q>(sb, es, ee, A, ae);
-            if ((tid & 63) == 0) finish_row(r, double(ee - es), A, ae);
+            if ((tid & 63) == 0) {
+                SWEEP_ROW_FACTOR(r, A, ae)
+                finish_row(r, double(ee - es), A, ae);
+            }
         }
     }
     __syncthreads();
@@ -180,6 +187,7 @@
                         for (int q = 0; q < Q; ++q) cav[q] *= sb[e * Q + q];
                         x_norm<Q>(cav, ce);
                     }
+                    SWEEP_ROW_FACTOR(r, cav, ce)
                     tot = apply_field_x<Q>(P, dc, di, cav, ce);
                 }
                 const double inv = 1.0 / tot;
