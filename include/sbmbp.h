@@ -258,7 +258,8 @@ typedef struct sbmbp_stats {
     uint64_t sweeps;             /* synchronous sweeps executed so far */
     uint64_t edge_msg_updates;   /* sweeps * E2 */
     double sweep_kernel_ms;      /* HIP-event time of the sweep kernels (sum) on the engine's stream */
-    uint64_t sweep_launches;     /* number of sweep-kernel launches timed */
+    uint64_t sweep_launches;     /* sweeps timed: one event pair per sweep (under sweep order 1 around its whole launch sequence).
+                                  * A shard times every chunk that has segments: the pairs of a call / n_chunks, rounded down */
     double bytes_per_sweep;      /* algorithmic bytes of one sweep */
     uint64_t device_bytes;       /* HBM held by this engine */
     uint32_t n_blocks;           /* workgroups of one sweep launch */

@@ -236,6 +236,58 @@ inline size_t rec_len(const sbmbp_engine *e) { return e->wide ? e->Q : e->Q - 1;
     }
 #endif
 
+// The label count and ONE run-time bool bound together: the statement sees QQ (QT) and `constexpr bool BB`, so a kernel with
+// a bool template parameter is launched by one statement with one argument list.
+#define DISPATCH_QB(Qv, flag, ...)                                                      \
+    do {                                                                                \
+        if (flag) { DISPATCH_Q(Qv, { constexpr bool BB = true; __VA_ARGS__; }) }        \
+        else { DISPATCH_Q(Qv, { constexpr bool BB = false; __VA_ARGS__; }) }            \
+    } while (0)
+#define DISPATCH_QTB(Qv, flag, ...)                                                     \
+    do {                                                                                \
+        if (flag) { DISPATCH_QT(Qv, { constexpr bool BB = true; __VA_ARGS__; }) }       \
+        else { DISPATCH_QT(Qv, { constexpr bool BB = false; __VA_ARGS__; }) }           \
+    } while (0)
+
+// Kernels that exist for a range of label counts only (k_fe_psi<Q, true> up to 8, k_em_edges_batch above EM_FRAME_QMAX) are
+// named with q_clamp(QQ, lo, hi) in a dispatch: outside the range, where a run-time test keeps the launch from happening,
+// the statement names an instantiation that exists anyway and adds none.
+constexpr int q_clamp(int q, int lo, int hi) { return q < lo ? lo : (q > hi ? hi : q); }
+
+// Event pair around what a sweep times (collect_timing adds the pairs up). timing_begin grows the pool, records the first
+// event on st and leaves the second in *stop for timing_end; *stop is null when timing is off or there is nothing to time.
+int timing_begin(sbmbp_engine *e, hipStream_t st, bool anything, hipEvent_t *stop) {
+    *stop = nullptr;
+    if (!e->timing || !anything) return SBMBP_OK;
+    if (e->ev_used + 2 > e->ev.size()) {
+        size_t old = e->ev.size();
+        e->ev.resize(old + 256);
+        for (size_t i = old; i < e->ev.size(); ++i) HIPCHK(hipEventCreate(&e->ev[i]));
+    }
+    const hipEvent_t start = e->ev[e->ev_used++];
+    *stop = e->ev[e->ev_used++];
+    HIPCHK(hipEventRecord(start, st));
+    return SBMBP_OK;
+}
+int timing_end(hipEvent_t stop, hipStream_t st) {
+    if (stop) HIPCHK(hipEventRecord(stop, st));
+    return SBMBP_OK;
+}
+
+// The buffers of sweep j of the running call: message and marginal buffers alternate per sweep, from the engine's current pair.
+struct sweep_bufs {
+    int pc;  // index of the marginal table the sweep reads
+    const double *Mold;
+    double *Mnew;
+    const double *psi_old;
+    double *psi_new;
+    const int32_t *clamp;
+};
+sweep_bufs bufs_of_sweep(const sbmbp_engine *e, uint32_t j) {
+    const int mc = (e->cur + int(j)) & 1, pc = (e->pcur + int(j)) & 1;
+    return sweep_bufs{pc, e->d_M[mc], e->d_M[mc ^ 1], e->d_psi[pc], e->d_psi[pc ^ 1], e->has_clamp ? e->d_clamp : nullptr};
+}
+
 int upload_params(sbmbp_engine *e, double crit, bool hinted = false) {
     dev_params P;
     std::memset(&P, 0, sizeof P);
@@ -386,13 +438,8 @@ int launch_hub_msg(sbmbp_engine *e, hipStream_t st, const double *Mold, double *
     if (!e->n_hub) return SBMBP_OK;
     const uint32_t nf = e->n_frag;
     const hub_frags hf{e->d_frag_hub, e->d_hub_frag0, e->d_hub_b, e->d_hub_pA, e->d_hub_pE};
-    if (e->dc == 2) {
-        DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_frag_product_msg<QQ, true>), dim3(nf), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev, e->d_nbr,
-                                            e->d_deg, Mold, e->d_hub_row, e->d_hub_blk, hf, 0u, e->d_P, e->d_partials, clamp));
-    } else {
-        DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_frag_product_msg<QQ, false>), dim3(nf), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev, e->d_nbr,
-                                            e->d_deg, Mold, e->d_hub_row, e->d_hub_blk, hf, 0u, e->d_P, e->d_partials, clamp));
-    }
+    DISPATCH_QB(e->Q, e->dc == 2, hipLaunchKernelGGL((k_hub_frag_product_msg<QQ, BB>), dim3(nf), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev, e->d_nbr,
+                                                     e->d_deg, Mold, e->d_hub_row, e->d_hub_blk, hf, 0u, e->d_P, e->d_partials, clamp));
     DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_frag_cavity_msg<QQ>), dim3(nf), dim3(BLOCK), 0, st, e->d_row_ptr, Mold, Mnew, psi_old, psi_new,
                                         e->d_hub_row, e->d_hub_blk, hf, 0u, e->d_P, int(e->dc != 0), damp,
                                         e->d_partials, clamp, e->d_prior));
@@ -429,27 +476,13 @@ int launch_field(sbmbp_engine *e, int mode) {
 // sweep). psi_form: reconstruct incoming messages from the neighbours' marginals (k_sweep_psi)
 // instead of gathering them from the message array (k_sweep).
 int launch_sweep(sbmbp_engine *e, uint32_t j, double damp, bool psi_form, bool first_from_psi = false) {
-    const int mc = (e->cur + int(j)) & 1, pc = (e->pcur + int(j)) & 1;
-    const double *Mold = e->d_M[mc];
-    double *Mnew = e->d_M[mc ^ 1];
-    const double *psi_old = e->d_psi[pc];
-    double *psi_new = e->d_psi[pc ^ 1];
-    const int32_t *clamp = e->has_clamp ? e->d_clamp : nullptr;
+    const sweep_bufs s = bufs_of_sweep(e, j);
+    hipEvent_t stop;
     if (e->wide) {  // Q > 16: one kernel for rows of any degree, then the fold and K2 for a run-time Q
-        hipEvent_t w0 = nullptr, w1 = nullptr;
-        if (e->timing) {
-            if (e->ev_used + 2 > e->ev.size()) {
-                size_t old = e->ev.size();
-                e->ev.resize(old + 256);
-                for (size_t i = old; i < e->ev.size(); ++i) HIPCHK(hipEventCreate(&e->ev[i]));
-            }
-            w0 = e->ev[e->ev_used++];
-            w1 = e->ev[e->ev_used++];
-            HIPCHK(hipEventRecord(w0, e->stream));
-        }
-        DISPATCH_QT(e->Q, hipLaunchKernelGGL((k_wsweep<QT>), dim3(e->n_blk), dim3(WTPB), 0, e->stream, e->d_row_ptr, e->d_rev, Mold, Mnew, psi_old,
-                                             psi_new, clamp, e->d_blk_row, e->d_blk_e0, e->d_P, e->d_Pw, int(e->Q), int(e->dc), damp, e->d_partials));
-        if (e->timing) HIPCHK(hipEventRecord(w1, e->stream));
+        CHK(timing_begin(e, e->stream, true, &stop));
+        DISPATCH_QT(e->Q, hipLaunchKernelGGL((k_wsweep<QT>), dim3(e->n_blk), dim3(WTPB), 0, e->stream, e->d_row_ptr, e->d_rev, s.Mold, s.Mnew, s.psi_old,
+                                             s.psi_new, s.clamp, e->d_blk_row, e->d_blk_e0, e->d_P, e->d_Pw, int(e->Q), int(e->dc), damp, e->d_partials));
+        CHK(timing_end(stop, e->stream));
         return launch_wfinalize(e, e->n_blk, 0);
     }
     // Hub rows first, in fragments, on the sweep's own stream (disjoint rows and edges from the frame kernel's; they are
@@ -457,51 +490,26 @@ int launch_sweep(sbmbp_engine *e, uint32_t j, double damp, bool psi_form, bool f
     // let the fragment PRODUCTS ride at the head of the frame launch instead of a launch of their own, and the frame kernel
     // grew by exactly the product kernel's 0.037 ms: the fragments cost what their edges cost wherever they run).
     if (e->n_hub) {
-        if (psi_form) CHK(launch_hub_psi(e, e->stream, 0, e->n_hub, Mnew, psi_old, psi_new, clamp, shard_io{}, Mold, int(first_from_psi)));
-        else CHK(launch_hub_msg(e, e->stream, Mold, Mnew, psi_old, psi_new, clamp, damp));
+        if (psi_form) CHK(launch_hub_psi(e, e->stream, 0, e->n_hub, s.Mnew, s.psi_old, s.psi_new, s.clamp, shard_io{}, s.Mold, int(first_from_psi)));
+        else CHK(launch_hub_msg(e, e->stream, s.Mold, s.Mnew, s.psi_old, s.psi_new, s.clamp, damp));
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (e->timing) {
-        if (e->ev_used + 2 > e->ev.size()) {
-            size_t old = e->ev.size();
-            e->ev.resize(old + 256);
-            for (size_t i = old; i < e->ev.size(); ++i) HIPCHK(hipEventCreate(&e->ev[i]));
-        }
-        e0 = e->ev[e->ev_used++];
-        e1 = e->ev[e->ev_used++];
-        HIPCHK(hipEventRecord(e0, e->stream));
-    }
+    CHK(timing_begin(e, e->stream, true, &stop));  // around the frame kernel only
     if (psi_form) {
-        if (clamp) {
-            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_psi<QQ, true, false>), dim3(xcd_grid(e->n_blk)), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_nbr,
-                                                Mnew, psi_old, psi_new, e->d_blk_row, e->d_blk_e0, e->d_P, int(e->dc), e->d_partials, clamp, shard_io{}, e->n_blk, SBMBP_XCD_REMAP,
-                                                Mold, int(first_from_psi)));
-        } else {
-            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_psi<QQ, false, false>), dim3(xcd_grid(e->n_blk)), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_nbr,
-                                                Mnew, psi_old, psi_new, e->d_blk_row, e->d_blk_e0, e->d_P, int(e->dc), e->d_partials,
-                                                (const int32_t *)nullptr, shard_io{}, e->n_blk, SBMBP_XCD_REMAP,
-                                                Mold, int(first_from_psi)));
-        }
+        DISPATCH_QB(e->Q, s.clamp != nullptr,
+                    hipLaunchKernelGGL((k_sweep_psi<QQ, BB, false>), dim3(xcd_grid(e->n_blk)), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_nbr,
+                                       s.Mnew, s.psi_old, s.psi_new, e->d_blk_row, e->d_blk_e0, e->d_P, int(e->dc), e->d_partials, s.clamp, shard_io{}, e->n_blk,
+                                       SBMBP_XCD_REMAP, s.Mold, int(first_from_psi)));
     } else if (e->d_prior != nullptr) {  // a per-vertex prior is set: the prior twin of k_sweep
-        if (e->dc == 2) {
-            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_prior<QQ, true>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
-                                                e->d_rev, e->d_nbr, e->d_deg, Mold, Mnew, psi_old, psi_new, clamp, e->d_blk_row, e->d_blk_e0, e->d_P,
-                                                1, damp, e->d_partials, e->d_prior));
-        } else {
-            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_prior<QQ, false>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
-                                                e->d_rev, e->d_nbr, e->d_deg, Mold, Mnew, psi_old, psi_new, clamp, e->d_blk_row, e->d_blk_e0, e->d_P,
-                                                int(e->dc), damp, e->d_partials, e->d_prior));
-        }
-    } else if (e->dc == 2) {
-        DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep<QQ, true>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
-                                            e->d_rev, e->d_nbr, e->d_deg, Mold, Mnew, psi_old, psi_new, clamp, e->d_blk_row, e->d_blk_e0, e->d_P,
-                                            1, damp, e->d_partials));
+        DISPATCH_QB(e->Q, e->dc == 2,
+                    hipLaunchKernelGGL((k_sweep_prior<QQ, BB>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
+                                       e->d_deg, s.Mold, s.Mnew, s.psi_old, s.psi_new, s.clamp, e->d_blk_row, e->d_blk_e0, e->d_P, int(e->dc != 0), damp,
+                                       e->d_partials, e->d_prior));
     } else {
-        DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep<QQ, false>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
-                                            e->d_rev, e->d_nbr, e->d_deg, Mold, Mnew, psi_old, psi_new, clamp, e->d_blk_row, e->d_blk_e0, e->d_P,
-                                            int(e->dc), damp, e->d_partials));
+        DISPATCH_QB(e->Q, e->dc == 2,
+                    hipLaunchKernelGGL((k_sweep<QQ, BB>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg,
+                                       s.Mold, s.Mnew, s.psi_old, s.psi_new, s.clamp, e->d_blk_row, e->d_blk_e0, e->d_P, int(e->dc != 0), damp, e->d_partials));
     }
-    if (e->timing) HIPCHK(hipEventRecord(e1, e->stream));
+    CHK(timing_end(stop, e->stream));
     // fold of the segment records + K2 in one launch (k_fold_finalize): <= FOLD_BLOCKS workgroups of >= 2048 records each
     if (!e->d_fold_counters) {
         CHK(dev_alloc(e, &e->d_fold_counters, 1));
@@ -634,47 +642,26 @@ int build_coloured(sbmbp_engine *e, const std::vector<uint32_t> &step, uint32_t 
 int launch_coloured_sweep(sbmbp_engine *e, double damp) {
     double *M = e->d_M[e->cur], *psi = e->d_psi[e->pcur];
     const int32_t *clamp = e->has_clamp ? e->d_clamp : nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (e->timing) {  // one pair per sweep: the step kernels AND their finalize launches (a sweep is nothing but their sequence)
-        if (e->ev_used + 2 > e->ev.size()) {
-            size_t old = e->ev.size();
-            e->ev.resize(old + 256);
-            for (size_t i = old; i < e->ev.size(); ++i) HIPCHK(hipEventCreate(&e->ev[i]));
-        }
-        e0 = e->ev[e->ev_used++];
-        e1 = e->ev[e->ev_used++];
-        HIPCHK(hipEventRecord(e0, e->stream));
-    }
+    hipEvent_t stop;  // one pair per sweep: the step kernels AND their finalize launches (a sweep is nothing but their sequence)
+    CHK(timing_begin(e, e->stream, true, &stop));
     const hub_frags hf{e->d_cs_frag_hub, e->d_cs_hub_frag0, e->d_hub_b, e->d_hub_pA, e->d_hub_pE};
     for (uint32_t s = 0; s < e->cs_steps; ++s) {
         const uint32_t seg0 = e->cs_seg0[s], nseg = e->cs_seg0[s + 1] - seg0, nh = e->cs_hub0[s + 1] - e->cs_hub0[s];
         if (nh) {
             const uint32_t f0 = e->cs_frag0[s], nf = e->cs_frag0[s + 1] - f0;
-            if (e->dc == 2) {
-                DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_frag_product_msg<QQ, true>), dim3(nf), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
-                                                    e->d_deg, M, e->d_cs_hub_row, e->d_cs_hub_rec, hf, f0, e->d_P, e->d_partials, clamp));
-            } else {
-                DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_frag_product_msg<QQ, false>), dim3(nf), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
-                                                    e->d_deg, M, e->d_cs_hub_row, e->d_cs_hub_rec, hf, f0, e->d_P, e->d_partials, clamp));
-            }
+            DISPATCH_QB(e->Q, e->dc == 2, hipLaunchKernelGGL((k_hub_frag_product_msg<QQ, BB>), dim3(nf), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev,
+                                                             e->d_nbr, e->d_deg, M, e->d_cs_hub_row, e->d_cs_hub_rec, hf, f0, e->d_P, e->d_partials, clamp));
             DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_step_cavity<QQ>), dim3(nf), dim3(BLOCK), 0, e->stream, e->d_row_ptr, M, psi, e->d_cs_hub_row,
                                                 e->d_cs_hub_rec, hf, f0, e->d_P, int(e->dc != 0), damp, e->d_partials, clamp));
         }
-        if (nseg) {
-            if (e->dc == 2) {
-                DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_step<QQ, true>), dim3(nseg), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev,
-                                                    e->d_nbr, e->d_deg, M, psi, clamp, e->d_cs_rows, e->d_cs_loff, e->d_cs_seg_row0, seg0, e->d_P, 1, damp,
-                                                    e->d_partials));
-            } else {
-                DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_step<QQ, false>), dim3(nseg), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev,
-                                                    e->d_nbr, e->d_deg, M, psi, clamp, e->d_cs_rows, e->d_cs_loff, e->d_cs_seg_row0, seg0, e->d_P, int(e->dc),
-                                                    damp, e->d_partials));
-            }
-        }
+        if (nseg)
+            DISPATCH_QB(e->Q, e->dc == 2, hipLaunchKernelGGL((k_sweep_step<QQ, BB>), dim3(nseg), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev,
+                                                             e->d_nbr, e->d_deg, M, psi, clamp, e->d_cs_rows, e->d_cs_loff, e->d_cs_seg_row0, seg0, e->d_P,
+                                                             int(e->dc != 0), damp, e->d_partials));
         DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_step_finalize<QQ>), dim3(1), dim3(BLOCK), 0, e->stream, e->d_partials, nseg + nh, int(s + 1 == e->cs_steps),
                                             e->d_P, e->d_hist, e->hist_cap));
     }
-    if (e->timing) HIPCHK(hipEventRecord(e1, e->stream));
+    CHK(timing_end(stop, e->stream));
     HIPCHK(hipGetLastError());
     return SBMBP_OK;
 }
@@ -883,15 +870,9 @@ int fused_pass(sbmbp_engine *e, bool want_entropy, bool want_em) {
     if (e->wide) {  // Q > 16: k_wreduce (message-gather, matrix cores), hub rows included
         CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (WR_NP + 1)));
         CHK(ensure_small(e, WR_NP));
-        if (want_entropy) {
-            DISPATCH_QT(Q, hipLaunchKernelGGL((k_wreduce<QT, true>), dim3(e->n_blk), dim3(WTPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
-                                              e->d_M[e->cur], e->d_psi[e->pcur], e->d_blk_row, e->d_blk_e0, e->d_P, e->d_Pw, int(Q), int(e->dc),
-                                              adj_mode, d_w, e->d_partials));
-        } else {
-            DISPATCH_QT(Q, hipLaunchKernelGGL((k_wreduce<QT, false>), dim3(e->n_blk), dim3(WTPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
-                                              e->d_M[e->cur], e->d_psi[e->pcur], e->d_blk_row, e->d_blk_e0, e->d_P, e->d_Pw, int(Q), int(e->dc),
-                                              adj_mode, d_w, e->d_partials));
-        }
+        DISPATCH_QTB(Q, want_entropy, hipLaunchKernelGGL((k_wreduce<QT, BB>), dim3(e->n_blk), dim3(WTPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
+                                                         e->d_M[e->cur], e->d_psi[e->pcur], e->d_blk_row, e->d_blk_e0, e->d_P, e->d_Pw, int(Q), int(e->dc),
+                                                         adj_mode, d_w, e->d_partials));
         HIPCHK(hipGetLastError());
         double o6[WR_NP];
         CHK(fold_to_host(e, e->n_blk, WR_NP, WR_NP + 1, o6));
@@ -908,15 +889,10 @@ int fused_pass(sbmbp_engine *e, bool want_entropy, bool want_em) {
     CHK(ensure_partials(e, size_t(std::max<uint32_t>(rows, 1)) * (NP + 1)));
     CHK(ensure_small(e, NP));
     const double *Mcur = e->d_M[e->cur], *Mprev = e->d_M[e->cur ^ 1], *psi = e->d_psi[e->pcur];
-    if (want_em) {
-        DISPATCH_Q(Q, hipLaunchKernelGGL((k_fe_psi<(QQ <= 8 ? QQ : 2), true>), dim3(xcd_grid(e->n_blk)), dim3(frame_cfg<(QQ <= 8 ? QQ : 2)>::TPB), 0, e->stream,
-                                         e->d_row_ptr, e->d_nbr, Mcur, Mprev, psi, e->d_blk_row, e->d_blk_e0, e->d_P, int(e->dc),
-                                         int(want_entropy), adj_mode, d_w, e->n_blk, e->d_partials));
-    } else {
-        DISPATCH_Q(Q, hipLaunchKernelGGL((k_fe_psi<QQ, false>), dim3(xcd_grid(e->n_blk)), dim3(frame_cfg<QQ>::TPB), 0, e->stream,
-                                         e->d_row_ptr, e->d_nbr, Mcur, Mprev, psi, e->d_blk_row, e->d_blk_e0, e->d_P, int(e->dc),
-                                         int(want_entropy), adj_mode, d_w, e->n_blk, e->d_partials));
-    }
+    // (want_em holds up to Q = 8 only, see above)
+    DISPATCH_QB(Q, want_em, constexpr int QF = BB ? q_clamp(QQ, 2, 8) : QQ;
+                hipLaunchKernelGGL((k_fe_psi<QF, BB>), dim3(xcd_grid(e->n_blk)), dim3(frame_cfg<QF>::TPB), 0, e->stream, e->d_row_ptr, e->d_nbr, Mcur, Mprev,
+                                   psi, e->d_blk_row, e->d_blk_e0, e->d_P, int(e->dc), int(want_entropy), adj_mode, d_w, e->n_blk, e->d_partials));
     if (e->n_hub)  // site and edge terms of the hub rows, in records of their own behind the segments'
         DISPATCH_Q(Q, hipLaunchKernelGGL((k_fe_hub<QQ, false>), dim3(e->n_hub), dim3(BLOCK), 0, e->stream, e->d_row_ptr,
                                          e->d_rev, e->d_nbr, e->d_deg, Mcur, (const double *)nullptr, e->d_hub_row, e->d_hub_blk, e->d_P,
@@ -943,39 +919,22 @@ int site_edge_terms(sbmbp_engine *e, bool want_entropy, double out[4], double *d
     CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (FE_NP + 1)));
     const double *M = e->d_M[e->cur];
     const double *Min = (e->sharded && e->incoming_src == 0) ? e->d_Min : nullptr;
+    const bool dc2 = e->dc == 2;
+    const int dcf = int(e->dc != 0);  // (the DC2 variants take 1, the others dc, which is 0 or 1 there)
     if (e->d_prior != nullptr) {  // a per-vertex prior is set: the prior twins, whose site products take the row's prior line
-        if (e->dc == 2) {
-            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_fe_frame_prior<QQ, true>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
-                                                e->d_rev, e->d_nbr, e->d_deg, M, Min, e->d_blk_row, e->d_blk_e0, e->d_P, 1, int(want_entropy), e->d_partials,
-                                                e->d_prior));
-            if (e->n_hub)
-                DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_fe_hub_prior<QQ, true>), dim3(e->n_hub), dim3(BLOCK), 0, e->stream, e->d_row_ptr,
-                                                    e->d_rev, e->d_nbr, e->d_deg, M, Min, e->d_hub_row, e->d_hub_blk, e->d_P, 1,
-                                                    int(want_entropy), e->d_partials, uint32_t(FE_NP + 1), 0xffffffffu, e->d_prior));
-        } else {
-            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_fe_frame_prior<QQ, false>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
-                                                e->d_rev, e->d_nbr, e->d_deg, M, Min, e->d_blk_row, e->d_blk_e0, e->d_P, int(e->dc), int(want_entropy),
-                                                e->d_partials, e->d_prior));
-            if (e->n_hub)
-                DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_fe_hub_prior<QQ, false>), dim3(e->n_hub), dim3(BLOCK), 0, e->stream, e->d_row_ptr,
-                                                    e->d_rev, e->d_nbr, e->d_deg, M, Min, e->d_hub_row, e->d_hub_blk, e->d_P, int(e->dc),
-                                                    int(want_entropy), e->d_partials, uint32_t(FE_NP + 1), 0xffffffffu, e->d_prior));
-        }
-    } else if (e->dc == 2) {
-        DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_fe_frame<QQ, true>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
-                                            e->d_rev, e->d_nbr, e->d_deg, M, Min, e->d_blk_row, e->d_blk_e0, e->d_P, 1, int(want_entropy), e->d_partials));
+        DISPATCH_QB(e->Q, dc2, hipLaunchKernelGGL((k_fe_frame_prior<QQ, BB>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev,
+                                                  e->d_nbr, e->d_deg, M, Min, e->d_blk_row, e->d_blk_e0, e->d_P, dcf, int(want_entropy), e->d_partials, e->d_prior));
         if (e->n_hub)
-            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_fe_hub<QQ, true>), dim3(e->n_hub), dim3(BLOCK), 0, e->stream, e->d_row_ptr,
-                                                e->d_rev, e->d_nbr, e->d_deg, M, Min, e->d_hub_row, e->d_hub_blk, e->d_P, 1,
-                                                int(want_entropy), e->d_partials, uint32_t(FE_NP + 1), 0xffffffffu));
+            DISPATCH_QB(e->Q, dc2, hipLaunchKernelGGL((k_fe_hub_prior<QQ, BB>), dim3(e->n_hub), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
+                                                      e->d_deg, M, Min, e->d_hub_row, e->d_hub_blk, e->d_P, dcf, int(want_entropy), e->d_partials,
+                                                      uint32_t(FE_NP + 1), 0xffffffffu, e->d_prior));
     } else {
-        DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_fe_frame<QQ, false>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
-                                            e->d_rev, e->d_nbr, e->d_deg, M, Min, e->d_blk_row, e->d_blk_e0, e->d_P, int(e->dc), int(want_entropy),
-                                            e->d_partials));
+        DISPATCH_QB(e->Q, dc2, hipLaunchKernelGGL((k_fe_frame<QQ, BB>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
+                                                  e->d_deg, M, Min, e->d_blk_row, e->d_blk_e0, e->d_P, dcf, int(want_entropy), e->d_partials));
         if (e->n_hub)
-            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_fe_hub<QQ, false>), dim3(e->n_hub), dim3(BLOCK), 0, e->stream, e->d_row_ptr,
-                                                e->d_rev, e->d_nbr, e->d_deg, M, Min, e->d_hub_row, e->d_hub_blk, e->d_P, int(e->dc),
-                                                int(want_entropy), e->d_partials, uint32_t(FE_NP + 1), 0xffffffffu));
+            DISPATCH_QB(e->Q, dc2, hipLaunchKernelGGL((k_fe_hub<QQ, BB>), dim3(e->n_hub), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
+                                                      e->d_deg, M, Min, e->d_hub_row, e->d_hub_blk, e->d_P, dcf, int(want_entropy), e->d_partials,
+                                                      uint32_t(FE_NP + 1), 0xffffffffu));
     }
     HIPCHK(hipGetLastError());
     if (d_out) return fold_to_device(e, e->n_blk, FE_NP, FE_NP + 1, d_out);
@@ -1089,13 +1048,8 @@ int em_expect(sbmbp_engine *e, double *na_e, double *nna_e, double *cab_e) {
     // sbmbp_set_params uploads, and inside learning the preceding converge uploaded.
     const double *M = e->d_M[e->cur];
     const double *Min = (e->sharded && e->incoming_src == 0) ? e->d_Min : nullptr;
-    if (e->dc == 2) {
-        DISPATCH_Q(Q, hipLaunchKernelGGL((k_em_edges<QQ, true>), dim3(nb), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev,
-                                         e->d_nbr, e->d_deg, e->d_src, M, Min, uint32_t(e->E2), e->d_P, e->d_partials));
-    } else {
-        DISPATCH_Q(Q, hipLaunchKernelGGL((k_em_edges<QQ, false>), dim3(nb), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev,
-                                         e->d_nbr, e->d_deg, e->d_src, M, Min, uint32_t(e->E2), e->d_P, e->d_partials));
-    }
+    DISPATCH_QB(Q, e->dc == 2, hipLaunchKernelGGL((k_em_edges<QQ, BB>), dim3(nb), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev,
+                                                  e->d_nbr, e->d_deg, e->d_src, M, Min, uint32_t(e->E2), e->d_P, e->d_partials));
     HIPCHK(hipGetLastError());
     CHK(fold_to_host(e, nb, T, T + 1, tri.data()));
     }
@@ -1992,35 +1946,16 @@ int sbmbp_shard_sweep_explicit(sbmbp_engine_t *e, uint32_t j, double damping) {
     device_scope dev_(e);
     IS_SHARD(e);
     if (!e->d_rev) { set_error("shard was created without a reverse index"); return SBMBP_ERR_STATE; }
-    const int mc = (e->cur + int(j)) & 1, pc = (e->pcur + int(j)) & 1;
-    const double *Mold = e->d_M[mc];
-    double *Mnew = e->d_M[mc ^ 1];
-    const double *psi_old = e->d_psi[pc];
-    double *psi_new = e->d_psi[pc ^ 1];
-    const int32_t *clamp = e->has_clamp ? e->d_clamp : nullptr;
+    const sweep_bufs s = bufs_of_sweep(e, j);
     CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (e->Q + 1)));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (e->timing && e->n_blk) {
-        if (e->ev_used + 2 > e->ev.size()) {
-            size_t old = e->ev.size();
-            e->ev.resize(old + 256);
-            for (size_t i = old; i < e->ev.size(); ++i) HIPCHK(hipEventCreate(&e->ev[i]));
-        }
-        e0 = e->ev[e->ev_used++];
-        e1 = e->ev[e->ev_used++];
-        HIPCHK(hipEventRecord(e0, e->stream));
-    }
-    if (e->n_blk) {
-        if (e->dc == 2) {
-            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep<QQ, true>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
-                                                e->d_deg, Mold, Mnew, psi_old, psi_new, clamp, e->d_blk_row, e->d_blk_e0, e->d_P, 1, damping, e->d_partials));
-        } else {
-            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep<QQ, false>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
-                                                e->d_deg, Mold, Mnew, psi_old, psi_new, clamp, e->d_blk_row, e->d_blk_e0, e->d_P, int(e->dc), damping, e->d_partials));
-        }
-    }
-    if (e0) HIPCHK(hipEventRecord(e1, e->stream));
-    CHK(launch_hub_msg(e, e->stream, Mold, Mnew, psi_old, psi_new, clamp, damping));
+    hipEvent_t stop;
+    CHK(timing_begin(e, e->stream, e->n_blk != 0, &stop));
+    if (e->n_blk)
+        DISPATCH_QB(e->Q, e->dc == 2,
+                    hipLaunchKernelGGL((k_sweep<QQ, BB>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg,
+                                       s.Mold, s.Mnew, s.psi_old, s.psi_new, s.clamp, e->d_blk_row, e->d_blk_e0, e->d_P, int(e->dc != 0), damping, e->d_partials));
+    CHK(timing_end(stop, e->stream));
+    CHK(launch_hub_msg(e, e->stream, s.Mold, s.Mnew, s.psi_old, s.psi_new, s.clamp, damping));
     HIPCHK(hipGetLastError());
     return SBMBP_OK;
 }
@@ -2130,52 +2065,36 @@ int sbmbp_shard_sweep_chunk_on(sbmbp_engine_t *e, uint32_t j, uint32_t c, void *
     IS_SHARD(e);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     if (c + 1 >= e->chunk_blk.size()) { set_error("chunk index out of range"); return SBMBP_ERR_ARG; }
-    const int mc = (e->cur + int(j)) & 1, pc = (e->pcur + int(j)) & 1;
-    double *Mio = e->d_M[mc ^ 1];
-    const double *Mcmp = e->d_M[mc];  // read only once the exact criterion is armed (dev_params::exact)
+    // s.Mnew is read and written in place; s.Mold is read only once the exact criterion is armed (dev_params::exact); the
+    // chunk kernels take no clamp vector
+    const sweep_bufs s = bufs_of_sweep(e, j);
     const int first = (j == 0 && e->init_from_psi) ? 1 : 0;
-    const double *psi_old = e->d_psi[pc];
-    double *psi_new = e->d_psi[pc ^ 1];
     shard_io io;
     std::memset(&io, 0, sizeof io);
     if (e->d_snd_ptr) {  // fused exchange buffers: gather the halo of table pc from its receive buffer, drop new marginals into the send slots
         io.snd_ptr = e->d_snd_ptr;
         io.snd_slot = e->d_snd_slot;
         io.sendbuf = e->io_sendbuf;
-        io.halo_stage = e->io_stage[pc];
+        io.halo_stage = e->io_stage[s.pc];
         io.n_own = e->N;
         io.ncomp = int(e->io_ncomp);
     }
     CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (e->Q + 1)));
     const uint32_t b0 = e->chunk_blk[c], nb = e->chunk_blk[c + 1] - b0;
     const uint32_t h0 = e->chunk_hub[c], nh = e->chunk_hub[c + 1] - h0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (e->timing && nb) {
-        if (e->ev_used + 2 > e->ev.size()) {
-            size_t old = e->ev.size();
-            e->ev.resize(old + 256);
-            for (size_t i = old; i < e->ev.size(); ++i) HIPCHK(hipEventCreate(&e->ev[i]));
-        }
-        e0 = e->ev[e->ev_used++];
-        e1 = e->ev[e->ev_used++];
-        HIPCHK(hipEventRecord(e0, stream));
-    }
-    // XCD-aware numbering of the chunk launches too (1 chunk 0.371 -> 0.363 ms, 4 chunks 0.419 -> 0.412 ms per rank of the 8-rank C3 plan)
+    hipEvent_t stop;
+    CHK(timing_begin(e, stream, nb != 0, &stop));  // per chunk, and only a chunk that has segments
+    // XCD-aware numbering of the chunk launches too (1 chunk 0.371 -> 0.363 ms, 4 chunks 0.419 -> 0.412 ms per rank of the 8-rank C3 plan):
+    // with the fused exchange buffers only
     static const int shard_xcd = std::getenv("SBMBP_SHARD_XCD") ? std::atoi(std::getenv("SBMBP_SHARD_XCD")) : SBMBP_XCD_REMAP;
+    const int xcd = io.snd_ptr ? shard_xcd : 0;
     if (nb)
-    {
-        if (io.snd_ptr) {
-            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_psi<QQ, false, true>), dim3(shard_xcd ? xcd_grid(nb) : nb), dim3(frame_cfg<QQ>::TPB), 0, stream, e->d_row_ptr, e->d_nbr, Mio,
-                                                psi_old, psi_new, e->d_blk_row + b0, e->d_blk_e0 + b0, e->d_P, int(e->dc),
-                                                e->d_partials + size_t(b0) * (e->Q + 1), (const int32_t *)nullptr, io, nb, shard_xcd, Mcmp, first));
-        } else {
-            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_psi<QQ, false, false>), dim3(nb), dim3(frame_cfg<QQ>::TPB), 0, stream, e->d_row_ptr, e->d_nbr, Mio,
-                                                psi_old, psi_new, e->d_blk_row + b0, e->d_blk_e0 + b0, e->d_P, int(e->dc),
-                                                e->d_partials + size_t(b0) * (e->Q + 1), (const int32_t *)nullptr, io, nb, 0, Mcmp, first));
-        }
-    }
-    if (e->timing && nb) HIPCHK(hipEventRecord(e1, stream));
-    CHK(launch_hub_psi(e, stream, h0, nh, Mio, psi_old, psi_new, (const int32_t *)nullptr, io, Mcmp, first));
+        DISPATCH_QB(e->Q, io.snd_ptr != nullptr,
+                    hipLaunchKernelGGL((k_sweep_psi<QQ, false, BB>), dim3(xcd ? xcd_grid(nb) : nb), dim3(frame_cfg<QQ>::TPB), 0, stream, e->d_row_ptr, e->d_nbr,
+                                       s.Mnew, s.psi_old, s.psi_new, e->d_blk_row + b0, e->d_blk_e0 + b0, e->d_P, int(e->dc),
+                                       e->d_partials + size_t(b0) * (e->Q + 1), (const int32_t *)nullptr, io, nb, xcd, s.Mold, first));
+    CHK(timing_end(stop, stream));
+    CHK(launch_hub_psi(e, stream, h0, nh, s.Mnew, s.psi_old, s.psi_new, (const int32_t *)nullptr, io, s.Mold, first));
     HIPCHK(hipGetLastError());
     return SBMBP_OK;
 }
@@ -2377,13 +2296,8 @@ int sbmbp_shard_em_partial(sbmbp_engine_t *e, uint32_t *n_values) {
     const uint32_t nb = uint32_t(std::min<uint64_t>(2048, std::max<uint64_t>(1, (e->E2 + BLOCK - 1) / BLOCK)));
     CHK(ensure_partials(e, size_t(nb) * (T + 1)));
     const double *Min = e->incoming_src == 0 ? e->d_Min : nullptr;
-    if (e->dc == 2) {
-        DISPATCH_Q(Q, hipLaunchKernelGGL((k_em_edges<QQ, true>), dim3(nb), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg,
-                                         e->d_src, e->d_M[e->cur], Min, uint32_t(e->E2), e->d_P, e->d_partials));
-    } else {
-        DISPATCH_Q(Q, hipLaunchKernelGGL((k_em_edges<QQ, false>), dim3(nb), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg,
-                                         e->d_src, e->d_M[e->cur], Min, uint32_t(e->E2), e->d_P, e->d_partials));
-    }
+    DISPATCH_QB(Q, e->dc == 2, hipLaunchKernelGGL((k_em_edges<QQ, BB>), dim3(nb), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg,
+                                                  e->d_src, e->d_M[e->cur], Min, uint32_t(e->E2), e->d_P, e->d_partials));
     HIPCHK(hipGetLastError());
     CHK(fold_to_device(e, nb, T, T + 1, e->d_red + R));
     *n_values = R + T;
@@ -2507,15 +2421,9 @@ int batch_launch_sweep(sbmbp_batch *b, const batch_view &bv, uint32_t j, double 
         CHK(r_);
     }
     const dim3 grid(e->n_blk, b->R);
-    if (e->dc == 2) {
-        DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_batch<QQ, true>), grid, dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
-                                            e->d_deg, clamp, e->d_blk_row, e->d_blk_e0, bv.M, bv.psi, bv.P, bv.rec, bv.par, bv.msg_stride, bv.psi_stride,
-                                            bv.rec_stride, bv.R, j, 1, damp));
-    } else {
-        DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_sweep_batch<QQ, false>), grid, dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
-                                            e->d_deg, clamp, e->d_blk_row, e->d_blk_e0, bv.M, bv.psi, bv.P, bv.rec, bv.par, bv.msg_stride, bv.psi_stride,
-                                            bv.rec_stride, bv.R, j, int(e->dc), damp));
-    }
+    DISPATCH_QB(e->Q, e->dc == 2, hipLaunchKernelGGL((k_sweep_batch<QQ, BB>), grid, dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
+                                                     e->d_deg, clamp, e->d_blk_row, e->d_blk_e0, bv.M, bv.psi, bv.P, bv.rec, bv.par, bv.msg_stride, bv.psi_stride,
+                                                     bv.rec_stride, bv.R, j, int(e->dc != 0), damp));
     DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_finalize_batch<QQ>), dim3(b->R), dim3(BLOCK), 0, e->stream, bv.P, bv.rec, bv.rec_stride, e->n_blk));
     HIPCHK(hipGetLastError());
     return SBMBP_OK;
@@ -2696,41 +2604,28 @@ int batch_reductions(sbmbp_batch *b, const uint8_t *mask, double *na_e, double *
         DISPATCH_Q(Q, hipLaunchKernelGGL((k_field_refresh_batch<QQ>), dim3(R), dim3(BLOCK), 0, st, b->d_P, d_ref, b->d_em_part[0], nbf));
     }
     const dim3 fgrid(e->n_blk, R);
-#define EM_FRAME(QV, DC2V, EMV, DCV)                                                                                                      \
-    hipLaunchKernelGGL((k_em_frame_batch<QV, DC2V, EMV>), fgrid, dim3(frame_cfg<QV>::TPB), 0, st, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg, \
-                       e->d_blk_row, e->d_blk_e0, b->d_M, b->d_psi, b->d_P, d_par, d_act, d_mats, b->msg_stride, b->psi_stride, R, DCV,    \
-                       adj_mode, rows, b->d_em_part[0])
-    if (e->dc == 2) {
-        DISPATCH_Q(Q, if (QQ <= EM_FRAME_QMAX) { EM_FRAME((QQ <= EM_FRAME_QMAX ? QQ : 2), true, true, 1); } else { EM_FRAME((QQ > EM_FRAME_QMAX ? QQ : 16), true, false, 1); });
-    } else {
-        DISPATCH_Q(Q, if (QQ <= EM_FRAME_QMAX) { EM_FRAME((QQ <= EM_FRAME_QMAX ? QQ : 2), false, true, int(e->dc)); } else { EM_FRAME((QQ > EM_FRAME_QMAX ? QQ : 16), false, false, int(e->dc)); });
-    }
-#undef EM_FRAME
+    const bool dc2 = e->dc == 2;
+    const int dcf = int(e->dc != 0);  // (the DC2 variants take 1, the others dc, which is 0 or 1 there)
+    // (the frame pass carries the numerators exactly for the label counts up to EM_FRAME_QMAX: EM is a function of QQ)
+    DISPATCH_QB(Q, dc2, hipLaunchKernelGGL((k_em_frame_batch<QQ, BB, (QQ <= EM_FRAME_QMAX)>), fgrid, dim3(frame_cfg<QQ>::TPB), 0, st, e->d_row_ptr, e->d_rev,
+                                           e->d_nbr, e->d_deg, e->d_blk_row, e->d_blk_e0, b->d_M, b->d_psi, b->d_P, d_par, d_act, d_mats, b->msg_stride,
+                                           b->psi_stride, R, dcf, adj_mode, rows, b->d_em_part[0]));
     if (e->n_hub)  // site and edge terms of the rows above a segment's capacity: k_fe_hub per replica on offset pointers
         for (uint32_t r = 0; r < R; ++r) {
             if (!h_act[r]) continue;
             const double *M = b->d_M + (size_t(h_par[r]) * R + r) * b->msg_stride;
             double *part = b->d_em_part[0] + size_t(r) * rows * NP;
-            if (e->dc == 2) {
-                DISPATCH_Q(Q, hipLaunchKernelGGL((k_fe_hub<QQ, true>), dim3(e->n_hub), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg, M,
-                                                 (const double *)nullptr, e->d_hub_row, e->d_hub_blk, b->d_P + r, 1, 0, part, NP, e->n_blk));
-            } else {
-                DISPATCH_Q(Q, hipLaunchKernelGGL((k_fe_hub<QQ, false>), dim3(e->n_hub), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg, M,
-                                                 (const double *)nullptr, e->d_hub_row, e->d_hub_blk, b->d_P + r, int(e->dc), 0, part, NP, e->n_blk));
-            }
+            DISPATCH_QB(Q, dc2, hipLaunchKernelGGL((k_fe_hub<QQ, BB>), dim3(e->n_hub), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg, M,
+                                                   (const double *)nullptr, e->d_hub_row, e->d_hub_blk, b->d_P + r, dcf, 0, part, NP, e->n_blk));
         }
     auto fold = [&](const double *in, uint32_t n_rows, uint32_t cols, uint32_t off) {
         hipLaunchKernelGGL(k_fold_batch, dim3((cols + BLOCK / 64 - 1) / (BLOCK / 64), R), dim3(BLOCK), 0, st, in, d_act, n_rows, cols, b->d_em_res, RES, off);
     };
     fold(b->d_em_part[0], rows, NP, 0);
     if (!em_in_frame) {
-        if (e->dc == 2) {
-            DISPATCH_Q(Q, hipLaunchKernelGGL((k_em_edges_batch<(QQ > EM_FRAME_QMAX ? QQ : 16), true>), dim3(nbe, R), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev,
-                                             e->d_nbr, e->d_deg, e->d_src, b->d_M, b->d_P, d_par, d_act, b->msg_stride, R, uint32_t(e->E2), b->d_em_part[1]));
-        } else {
-            DISPATCH_Q(Q, hipLaunchKernelGGL((k_em_edges_batch<(QQ > EM_FRAME_QMAX ? QQ : 16), false>), dim3(nbe, R), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev,
-                                             e->d_nbr, e->d_deg, e->d_src, b->d_M, b->d_P, d_par, d_act, b->msg_stride, R, uint32_t(e->E2), b->d_em_part[1]));
-        }
+        DISPATCH_QB(Q, dc2, hipLaunchKernelGGL((k_em_edges_batch<q_clamp(QQ, EM_FRAME_QMAX + 1, 16), BB>), dim3(nbe, R), dim3(BLOCK), 0, st, e->d_row_ptr,
+                                               e->d_rev, e->d_nbr, e->d_deg, e->d_src, b->d_M, b->d_P, d_par, d_act, b->msg_stride, R, uint32_t(e->E2),
+                                               b->d_em_part[1]));
         fold(b->d_em_part[1], nbe, T, uint32_t(EM_NA) + 2 * Q);
     }
     if (nonedge && exact) {
