@@ -136,7 +136,8 @@ int sbmbp_get_field(sbmbp_engine_t *e, double *h /* Q */); /* h_ of belief_propa
  * sbmbp_stats does not grow, the reductions take the message-form kernels, and bytes_per_sweep grows by 8 Q N.
  * SBMBP_ERR_ARG (before any device work; the message names the first offending vertex): a negative, NaN or Inf entry, a row
  * without a positive entry. SBMBP_ERR_UNSUPPORTED: Q > 16; a shard engine; an engine in the coloured sweep order - and
- * sbmbp_set_sweep_order(e, 1, ...) on an engine that holds a prior. Replica batches and sbmbp_dist_* take no prior.
+ * sbmbp_set_sweep_order(e, 1, ...) on an engine that holds a prior. Replica batches take theirs through
+ * sbmbp_batch_set_vertex_prior (one shared table or one per replica); sbmbp_dist_* take no prior.
  * sbmbp_get_vertex_prior: *present = 1 and the table copied into prior (N*Q, or NULL) when one is set, else *present = 0.
  * sbmbp_prior_load: host only, no device. Reads the text format "vertex w_0 ... w_{Q-1}", one line per annotated vertex in any
  * order, into a dense table (ones where no line names the vertex); *n_rows_given = lines read. SBMBP_ERR_IO: unreadable;
@@ -303,6 +304,38 @@ int sbmbp_batch_get_params(sbmbp_batch_t *b, uint32_t replica, double *cab, uint
 int sbmbp_batch_set_state(sbmbp_batch_t *b, uint32_t replica, const double *psi, const double *msg_out);
 int sbmbp_batch_get_state(sbmbp_batch_t *b, uint32_t replica, double *psi, double *msg_out);
 int sbmbp_batch_get_field(sbmbp_batch_t *b, uint32_t replica, double *h /* Q */);
+/* Per-vertex label priors of a batch. Every replica is in one of three states: NONE, SHARED (it reads the batch's one shared
+ * table) or OWN (a table of its own). prior: N*Q doubles as sbmbp_set_vertex_prior takes them, or NULL.
+ *   replica = -1, table: every replica becomes SHARED with this table, which is stored ONCE in HBM whatever R is; every own
+ *                        table is freed (mirrors sbmbp_batch_set_params(b, -1, ...))
+ *   replica = -1, NULL:  every replica becomes NONE and all tables are freed
+ *   replica = r, table:  replica r becomes OWN (this overrides the shared table for r)
+ *   replica = r, NULL:   replica r becomes NONE
+ * A table means for its replica exactly what sbmbp_set_vertex_prior documents for the single engine: it multiplies eta_q in
+ * the marginal, in every message sent and in the exact cavity fallback, and in the site terms of the free energy and of the
+ * entropy; it is not in h, the edge terms, the non-edge terms or the EM numerators; a zero forbids a label exactly; clamped
+ * rows ignore it; it is stored as given. The tables belong to the batch like the graph: they survive
+ * sbmbp_batch_init_messages*, sbmbp_batch_set_params and sbmbp_batch_set_state; setting or removing one drops what the batch
+ * caches about the replica's state. sbmbp_batch_learning and sbmbp_batch_em_step hold the priors fixed and apply the
+ * reference's rules unchanged. One use is a semi-supervised run from R starts (one shared table); another is R folds of a
+ * label hold-out, or one graph under R annotation sets, from one launch sequence (own tables).
+ * Two consequences:
+ * - While some replicas hold a table and others do not, those without one are advanced by the prior kernels over ONE table of
+ *   ones that the batch keeps (allocated on first need, N Q 8 bytes, freed when no replica or every replica holds a table).
+ *   Such a replica goes through the states of a single engine with an all-ones prior, bit for bit; that is the no-prior run
+ *   up to rounding (1e-13), not to the bit. A batch in which no replica holds a table launches exactly what it launches
+ *   without this call.
+ * - Scaling a row by c moves the free energy by -log(c)/N. *best of sbmbp_batch_inference / sbmbp_batch_learning compares
+ *   free energies as they are, so it compares like with like only among replicas that read the same table.
+ * bytes_per_sweep of sbmbp_batch_get_stats (one replica's) grows by 8 Q N while any replica holds a table; device_bytes
+ * counts every table.
+ * Errors, before any device work: SBMBP_ERR_ARG for a replica index outside -1 .. R-1 and for a bad row (a negative, NaN or
+ * Inf entry, no positive entry; the message names the vertex, and the replica when one was given); SBMBP_ERR_NOMEM for a
+ * table that does not fit, which leaves the batch as it was.
+ * sbmbp_batch_get_vertex_prior: *present = 0 NONE, 1 SHARED, 2 OWN; when it is not 0 the table is copied into prior (N*Q, or
+ * NULL). */
+int sbmbp_batch_set_vertex_prior(sbmbp_batch_t *b, int replica, const double *prior /* N*Q, or NULL */);
+int sbmbp_batch_get_vertex_prior(sbmbp_batch_t *b, uint32_t replica, double *prior /* N*Q or NULL */, int *present);
 int sbmbp_batch_get_relaxation(const sbmbp_batch_t *b, uint32_t replica, int *field_level, int *generic_level, double *field_mix,
                                double *damping_factor);
 /* common to all replicas */
@@ -325,7 +358,7 @@ int sbmbp_batch_em_expectations(sbmbp_batch_t *b, uint32_t replica, double *na_e
 int sbmbp_batch_inference(sbmbp_batch_t *b, float conv_crit, uint32_t time_conv, float dumping_rate, sbmbp_infer_result *out /* R */,
                           uint32_t *best);
 /* sweeps = sum over replicas of the sweeps actually executed, edge_msg_updates = sweeps * E2, psi_form_sweeps = 0;
- * bytes_per_sweep is one replica's; the kernel-time fields are 0 */
+ * bytes_per_sweep is one replica's (8 Q N more while any replica holds a prior table); the kernel-time fields are 0 */
 int sbmbp_batch_get_stats(sbmbp_batch_t *b, sbmbp_stats *out);
 
 /* Multi-start EM: belief_propagation::learning (belief_propagation.cpp:14-75) for every replica in lock-step rounds.

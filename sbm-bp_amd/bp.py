@@ -515,6 +515,29 @@ class ReplicaBatch:
         check(self._lib.sbmbp_batch_get_field(self._h, self._replica(replica), _dp(h)))
         return h
 
+    def set_vertex_prior(self, prior, replica=-1):
+        """per-vertex label priors (sbmbp.h sbmbp_batch_set_vertex_prior): an (N, Q) array as BeliefPropagation.set_vertex_prior
+        takes it, or None. replica = -1: every replica reads this ONE table (stored once), or with None all tables are removed;
+        replica = r: replica r gets a table of its own (overriding the shared one), or with None reads none"""
+        replica = int(replica)
+        if prior is None:
+            check(self._lib.sbmbp_batch_set_vertex_prior(self._h, replica, None))
+            return
+        pr = np.array(prior, dtype=np.float64, order="C")
+        if pr.shape != (self.N, self.Q):
+            raise ValueError("prior needs shape (N, Q)")
+        check(self._lib.sbmbp_batch_set_vertex_prior(self._h, replica, _dp(pr)))
+
+    def vertex_prior(self, replica):
+        """(state, table) of replica: state 0 = none (table None), 1 = the batch's shared table, 2 = its own; table (N, Q)"""
+        present = C.c_int(0)
+        check(self._lib.sbmbp_batch_get_vertex_prior(self._h, self._replica(replica), None, C.byref(present)))
+        if not present.value:
+            return 0, None
+        pr = np.zeros((self.N, self.Q))
+        check(self._lib.sbmbp_batch_get_vertex_prior(self._h, self._replica(replica), _dp(pr), C.byref(present)))
+        return present.value, pr
+
     def relaxation(self, replica):
         """(field level, generic level, field_mix, damping factor) replica's last converge call ended on"""
         fl, gl, mix, dmp = C.c_int(0), C.c_int(0), C.c_double(0.0), C.c_double(0.0)

@@ -126,6 +126,8 @@ SYMBOLS = {
     "sbmbp_batch_set_state": (C.c_int, [C.c_void_p, C.c_uint32, c_dp, c_dp]),
     "sbmbp_batch_get_state": (C.c_int, [C.c_void_p, C.c_uint32, c_dp, c_dp]),
     "sbmbp_batch_get_field": (C.c_int, [C.c_void_p, C.c_uint32, c_dp]),
+    "sbmbp_batch_set_vertex_prior": (C.c_int, [C.c_void_p, C.c_int, c_dp]),
+    "sbmbp_batch_get_vertex_prior": (C.c_int, [C.c_void_p, C.c_uint32, c_dp, C.POINTER(C.c_int)]),
     "sbmbp_batch_get_relaxation": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int), c_dp, c_dp]),
     "sbmbp_batch_set_schedule": (C.c_int, [C.c_void_p, C.c_double, C.c_uint32]),
     "sbmbp_batch_set_auto_relax": (C.c_int, [C.c_void_p, C.c_int]),

@@ -2335,6 +2335,8 @@ struct batch_replica {
     bool have_params = false, have_state = false, field_fresh = false, w_positive = false;
     int par = 0;                // which of the two buffers holds the current state
     int ar_fl = 0, ar_gl = -1;  // levels the last converge call ended on
+    int prior_state = 0;        // per-vertex prior (sbmbp_batch_set_vertex_prior): 0 = none, 1 = the batch's shared table, 2 = own
+    double *d_prior = nullptr;  // the own table [N*Q] (state 2)
 };
 struct sbmbp_batch {
     sbmbp_engine *e = nullptr;
@@ -2355,9 +2357,23 @@ struct sbmbp_batch {
     size_t em_part_cap[3] = {0, 0, 0}, em_res_cap = 0;
     void *h_em_in = nullptr, *h_em_res = nullptr;
     size_t h_em_res_cap = 0;
+    // per-vertex priors: the ONE table of the shared replicas, the table of ones that replicas without a table read while
+    // another replica holds one (allocated on first need), and per replica the table it reads (device, [R]; what
+    // k_sweep_batch_prior and k_em_frame_batch_prior index with blockIdx.y). n_prior = replicas that hold a table: while it is
+    // 0 the batch launches what it launches without this feature.
+    double *d_prior_shared = nullptr, *d_prior_ones = nullptr;
+    const double **d_prior_tab = nullptr;
+    uint32_t n_prior = 0;
 };
 
 namespace {
+
+// the prior table replica r reads: null while no replica of the batch holds one; else the shared table, its own, or the ones
+const double *batch_prior_of(const sbmbp_batch *b, uint32_t r) {
+    if (!b->n_prior) return nullptr;
+    const batch_replica &p = b->rep[r];
+    return p.prior_state == 2 ? p.d_prior : (p.prior_state == 1 ? b->d_prior_shared : b->d_prior_ones);
+}
 
 // binds the batch's engine to replica r for the lifetime of the object
 struct bound_replica {
@@ -2371,6 +2387,7 @@ struct bound_replica {
             e->d_psi[k] = b->d_psi + (size_t(k) * b->R + r) * b->psi_stride;
         }
         e->d_P = b->d_P + r;
+        e->d_prior = const_cast<double *>(batch_prior_of(b, r));  // the reductions and hub launches of the bound engine take the prior kernels
         e->cur = e->pcur = p.par;
         e->cab = p.cab; e->eta = p.eta; e->na = p.na; e->beta = p.beta;
         e->have_params = p.have_params; e->have_state = p.have_state; e->field_fresh = p.field_fresh; e->w_positive = p.w_positive;
@@ -2385,6 +2402,7 @@ struct bound_replica {
         p.par = e->cur;
         e->d_M[0] = e->d_M[1] = e->d_psi[0] = e->d_psi[1] = nullptr;
         e->d_P = nullptr;
+        e->d_prior = nullptr;  // the tables are the batch's
         e->have_state = e->have_params = false;
     }
 };
@@ -2412,18 +2430,26 @@ int batch_launch_sweep(sbmbp_batch *b, const batch_view &bv, uint32_t j, double 
         for (uint32_t r = 0; r < b->R && r_ == SBMBP_OK; ++r) {
             const int mc = (b->call_par[r] + int(j)) & 1;
             e->d_P = b->d_P + r;
+            e->d_prior = const_cast<double *>(batch_prior_of(b, r));
             e->d_partials = b->d_rec + size_t(r) * b->rec_stride;
             r_ = launch_hub_msg(e, e->stream, b->d_M + (size_t(mc) * b->R + r) * b->msg_stride, b->d_M + (size_t(mc ^ 1) * b->R + r) * b->msg_stride,
                                 b->d_psi + (size_t(mc) * b->R + r) * b->psi_stride, b->d_psi + (size_t(mc ^ 1) * b->R + r) * b->psi_stride, clamp, damp);
         }
         e->d_P = nullptr;
+        e->d_prior = nullptr;
         e->d_partials = keep;
         CHK(r_);
     }
     const dim3 grid(e->n_blk, b->R);
-    DISPATCH_QB(e->Q, e->dc == 2, hipLaunchKernelGGL((k_sweep_batch<QQ, BB>), grid, dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
-                                                     e->d_deg, clamp, e->d_blk_row, e->d_blk_e0, bv.M, bv.psi, bv.P, bv.rec, bv.par, bv.msg_stride, bv.psi_stride,
-                                                     bv.rec_stride, bv.R, j, int(e->dc != 0), damp));
+    if (b->n_prior) {  // a replica holds a per-vertex prior: the prior twin, every replica over the table d_prior_tab names for it
+        DISPATCH_QB(e->Q, e->dc == 2, hipLaunchKernelGGL((k_sweep_batch_prior<QQ, BB>), grid, dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev,
+                                                         e->d_nbr, e->d_deg, clamp, e->d_blk_row, e->d_blk_e0, bv.M, bv.psi, bv.P, bv.rec, bv.par, bv.msg_stride,
+                                                         bv.psi_stride, bv.rec_stride, j, int(e->dc != 0), damp, b->d_prior_tab));
+    } else {
+        DISPATCH_QB(e->Q, e->dc == 2, hipLaunchKernelGGL((k_sweep_batch<QQ, BB>), grid, dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr,
+                                                         e->d_deg, clamp, e->d_blk_row, e->d_blk_e0, bv.M, bv.psi, bv.P, bv.rec, bv.par, bv.msg_stride, bv.psi_stride,
+                                                         bv.rec_stride, bv.R, j, int(e->dc != 0), damp));
+    }
     DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_finalize_batch<QQ>), dim3(b->R), dim3(BLOCK), 0, e->stream, bv.P, bv.rec, bv.rec_stride, e->n_blk));
     HIPCHK(hipGetLastError());
     return SBMBP_OK;
@@ -2513,8 +2539,10 @@ void batch_free(sbmbp_batch *b) {
         b->e->d_M[0] = b->e->d_M[1] = b->e->d_psi[0] = b->e->d_psi[1] = nullptr;  // they pointed into the batch buffers
         b->e->d_P = nullptr;
     }
-    void *ptrs[] = {b->d_M, b->d_psi, b->d_rec, b->d_P, b->d_par, b->d_cs, b->d_em_in, b->d_em_part[0], b->d_em_part[1], b->d_em_part[2], b->d_em_res};
+    void *ptrs[] = {b->d_M, b->d_psi, b->d_rec, b->d_P, b->d_par, b->d_cs, b->d_em_in, b->d_em_part[0], b->d_em_part[1], b->d_em_part[2], b->d_em_res,
+                    b->d_prior_shared, b->d_prior_ones, b->d_prior_tab};
     for (void *p : ptrs) if (p) (void)hipFree(p);
+    for (batch_replica &p : b->rep) if (p.d_prior) (void)hipFree(p.d_prior);
     void *hptrs[] = {b->h_cs, b->h_em_in, b->h_em_res};
     for (void *p : hptrs) if (p) (void)hipHostFree(p);
     for (auto ev : b->ev_cs) if (ev) (void)hipEventDestroy(ev);
@@ -2607,16 +2635,28 @@ int batch_reductions(sbmbp_batch *b, const uint8_t *mask, double *na_e, double *
     const bool dc2 = e->dc == 2;
     const int dcf = int(e->dc != 0);  // (the DC2 variants take 1, the others dc, which is 0 or 1 there)
     // (the frame pass carries the numerators exactly for the label counts up to EM_FRAME_QMAX: EM is a function of QQ)
-    DISPATCH_QB(Q, dc2, hipLaunchKernelGGL((k_em_frame_batch<QQ, BB, (QQ <= EM_FRAME_QMAX)>), fgrid, dim3(frame_cfg<QQ>::TPB), 0, st, e->d_row_ptr, e->d_rev,
-                                           e->d_nbr, e->d_deg, e->d_blk_row, e->d_blk_e0, b->d_M, b->d_psi, b->d_P, d_par, d_act, d_mats, b->msg_stride,
-                                           b->psi_stride, R, dcf, adj_mode, rows, b->d_em_part[0]));
+    if (b->n_prior) {  // a replica holds a per-vertex prior: the prior twin, log Z_i of every row with the line of its replica's table
+        DISPATCH_QB(Q, dc2, hipLaunchKernelGGL((k_em_frame_batch_prior<QQ, BB, (QQ <= EM_FRAME_QMAX)>), fgrid, dim3(frame_cfg<QQ>::TPB), 0, st, e->d_row_ptr,
+                                               e->d_rev, e->d_nbr, e->d_deg, e->d_blk_row, e->d_blk_e0, b->d_M, b->d_psi, b->d_P, d_par, d_act, d_mats,
+                                               b->msg_stride, b->psi_stride, R, dcf, adj_mode, rows, b->d_em_part[0], b->d_prior_tab));
+    } else {
+        DISPATCH_QB(Q, dc2, hipLaunchKernelGGL((k_em_frame_batch<QQ, BB, (QQ <= EM_FRAME_QMAX)>), fgrid, dim3(frame_cfg<QQ>::TPB), 0, st, e->d_row_ptr, e->d_rev,
+                                               e->d_nbr, e->d_deg, e->d_blk_row, e->d_blk_e0, b->d_M, b->d_psi, b->d_P, d_par, d_act, d_mats, b->msg_stride,
+                                               b->psi_stride, R, dcf, adj_mode, rows, b->d_em_part[0]));
+    }
     if (e->n_hub)  // site and edge terms of the rows above a segment's capacity: k_fe_hub per replica on offset pointers
         for (uint32_t r = 0; r < R; ++r) {
             if (!h_act[r]) continue;
             const double *M = b->d_M + (size_t(h_par[r]) * R + r) * b->msg_stride;
             double *part = b->d_em_part[0] + size_t(r) * rows * NP;
-            DISPATCH_QB(Q, dc2, hipLaunchKernelGGL((k_fe_hub<QQ, BB>), dim3(e->n_hub), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg, M,
-                                                   (const double *)nullptr, e->d_hub_row, e->d_hub_blk, b->d_P + r, dcf, 0, part, NP, e->n_blk));
+            if (b->n_prior) {
+                DISPATCH_QB(Q, dc2, hipLaunchKernelGGL((k_fe_hub_prior<QQ, BB>), dim3(e->n_hub), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg,
+                                                       M, (const double *)nullptr, e->d_hub_row, e->d_hub_blk, b->d_P + r, dcf, 0, part, NP, e->n_blk,
+                                                       batch_prior_of(b, r)));
+            } else {
+                DISPATCH_QB(Q, dc2, hipLaunchKernelGGL((k_fe_hub<QQ, BB>), dim3(e->n_hub), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg, M,
+                                                       (const double *)nullptr, e->d_hub_row, e->d_hub_blk, b->d_P + r, dcf, 0, part, NP, e->n_blk));
+            }
         }
     auto fold = [&](const double *in, uint32_t n_rows, uint32_t cols, uint32_t off) {
         hipLaunchKernelGGL(k_fold_batch, dim3((cols + BLOCK / 64 - 1) / (BLOCK / 64), R), dim3(BLOCK), 0, st, in, d_act, n_rows, cols, b->d_em_res, RES, off);
@@ -2710,6 +2750,7 @@ int sbmbp_batch_create(sbmbp_batch_t **out, const sbmbp_graph_t *g, uint32_t Q, 
     if (r == SBMBP_OK) r = dev_alloc(e, &b->d_P, R);
     if (r == SBMBP_OK) r = dev_alloc(e, &b->d_par, R);
     if (r == SBMBP_OK) r = dev_alloc(e, &b->d_cs, R * (sizeof(conv_state) / 4));
+    if (r == SBMBP_OK) r = dev_alloc(e, &b->d_prior_tab, R);  // filled when a table is set; never read before
     hipError_t h = hipSuccess;
     if (r == SBMBP_OK) h = hipMemsetAsync(b->d_rec, 0, R * b->rec_stride * 8, e->stream);
     if (r == SBMBP_OK && h == hipSuccess) h = hipMemsetAsync(b->d_P, 0, R * sizeof(dev_params), e->stream);
@@ -2784,6 +2825,82 @@ int sbmbp_batch_get_state(sbmbp_batch_t *b, uint32_t replica, double *psi, doubl
     bound_replica v(b, replica);
     return sbmbp_get_state(b->e, psi, msg_out);
 }
+// ---- per-vertex priors of a batch: every replica reads no table, the batch's one shared table, or its own -------------
+int sbmbp_batch_set_vertex_prior(sbmbp_batch_t *b, int replica, const double *prior) {
+    BATCH_ARGS(b);
+    if (replica != -1) CHK(batch_replica_arg(b, replica));
+    sbmbp_engine *e = b->e;
+    const uint32_t R = b->R;
+    const size_t n = size_t(e->N) * e->Q;
+    if (prior) {
+        std::string why;
+        const uint32_t bad = first_bad_prior_row(prior, e->N, e->Q, &why);
+        if (bad < e->N) {
+            set_error("sbmbp_batch_set_vertex_prior: prior row of vertex " + std::to_string(bad) +
+                      (replica >= 0 ? " (replica " + std::to_string(replica) + ")" : std::string()) + ": " + why);
+            return SBMBP_ERR_ARG;
+        }
+    }
+    device_scope dev_(e);
+    // the states this call leaves: which tables are still read, and whether some replica needs the table of ones
+    std::vector<int> next(R);
+    uint32_t held = 0, shared = 0;
+    for (uint32_t r = 0; r < R; ++r) {
+        next[r] = (replica == -1 || uint32_t(replica) == r) ? (prior ? (replica == -1 ? 1 : 2) : 0) : b->rep[r].prior_state;
+        held += next[r] != 0;
+        shared += next[r] == 1;
+    }
+    const bool need_ones = held && held < R;
+    auto drop = [&](double **p) {
+        if (*p) { (void)hipFree(*p); *p = nullptr; e->device_bytes -= std::max<size_t>(n, 1) * 8; }
+    };
+    // allocations first: a table that does not fit leaves the batch as it was
+    double **slot = replica == -1 ? &b->d_prior_shared : &b->rep[replica].d_prior;
+    const bool fresh_ones = need_ones && !b->d_prior_ones;
+    if (fresh_ones) CHK(dev_alloc(e, &b->d_prior_ones, n));
+    if (prior && !*slot) {
+        const int rc = dev_alloc(e, slot, n);
+        if (rc != SBMBP_OK) { if (fresh_ones) drop(&b->d_prior_ones); return rc; }
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));  // nothing in flight reads a table that is overwritten or freed below
+    std::vector<double> ones;
+    if (fresh_ones) {
+        ones.assign(n, 1.0);
+        HIPCHK(hipMemcpyAsync(b->d_prior_ones, ones.data(), n * 8, hipMemcpyHostToDevice, e->stream));
+    }
+    if (prior) HIPCHK(hipMemcpyAsync(*slot, prior, n * 8, hipMemcpyHostToDevice, e->stream));
+    for (uint32_t r = 0; r < R; ++r) {
+        batch_replica &p = b->rep[r];
+        p.prior_state = next[r];
+        if (next[r] != 2) drop(&p.d_prior);
+    }
+    if (!shared) drop(&b->d_prior_shared);
+    if (!need_ones) drop(&b->d_prior_ones);
+    b->n_prior = held;
+    // (what the batch caches about a replica's state is its field, which no prior enters; the engine's caches, psi_consistent
+    // and the fused pass, are dropped whenever a replica is bound)
+    std::vector<const double *> tab(R, nullptr);
+    if (held) {
+        for (uint32_t r = 0; r < R; ++r) tab[r] = batch_prior_of(b, r);
+        HIPCHK(hipMemcpyAsync(b->d_prior_tab, tab.data(), size_t(R) * sizeof(const double *), hipMemcpyHostToDevice, e->stream));
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return SBMBP_OK;
+}
+int sbmbp_batch_get_vertex_prior(sbmbp_batch_t *b, uint32_t replica, double *prior, int *present) {
+    BATCH_ARGS(b);
+    CHK(batch_replica_arg(b, replica));
+    const batch_replica &p = b->rep[replica];
+    if (present) *present = p.prior_state;
+    if (prior && p.prior_state) {
+        sbmbp_engine *e = b->e;
+        device_scope dev_(e);
+        HIPCHK(hipMemcpyAsync(prior, p.prior_state == 2 ? p.d_prior : b->d_prior_shared, size_t(e->N) * e->Q * 8, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    return SBMBP_OK;
+}
+
 int sbmbp_batch_get_field(sbmbp_batch_t *b, uint32_t replica, double *h) {
     if (!b || !h) return arg_error(__func__, __LINE__);
     CHK(batch_replica_arg(b, replica));
@@ -2971,6 +3088,7 @@ int sbmbp_batch_get_stats(sbmbp_batch_t *b, sbmbp_stats *out) {
     out->sweeps = b->sweeps;  // replica-sweeps actually executed
     out->edge_msg_updates = b->sweeps * e->E2;
     out->bytes_per_sweep = double(e->E2) * (24.0 * e->Q + 4.0 + (e->dc == 2 ? 4.0 : 0.0)) + double(e->N) * (8.0 * e->Q + 8.0);  // of ONE replica
+    if (b->n_prior) out->bytes_per_sweep += 8.0 * e->Q * double(e->N);  // every row reads the line of its replica's table once
     out->device_bytes = e->device_bytes;
     out->n_blocks = e->n_blk;
     out->n_hub_rows = e->n_hub;

@@ -12,6 +12,8 @@
 // The same holds below the sweep: every batch kernel here is the replica's addressing, a call of the single engine's
 // __device__ rule in kernels.h (finalize_update, psi_row_add, em_edge_terms, moments_chunk, nonedge_pair_sums) and its
 // own final store. The stores stay apart because block_sum_store and block_reduce_store fold in different orders.
+// Per-vertex priors (sbmbp_batch_set_vertex_prior): k_sweep_batch_prior and k_em_frame_batch_prior are the twins of the two
+// kernels whose row products a prior line enters, over the same bodies; they find the table of replica r in prior_tab[r].
 #ifndef SBMBP_KERNELS_BATCH_H
 #define SBMBP_KERNELS_BATCH_H
 
@@ -62,6 +64,46 @@ k_sweep_batch(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__
 #define SWEEP_RECORD rec_all + size_t(rep) * rec_stride + size_t(blockIdx.x) * (Q + 1)
 #define SWEEP_ROW_START(r, v) _Pragma("unroll") for (int q = 0; q < Q; ++q) v[q] = 1.0;
 #define SWEEP_ROW_FACTOR(r, v, x)
+#include "sweep_msg_body.inc"
+#undef SWEEP_REPLICA
+#undef SWEEP_MOLD
+#undef SWEEP_PSI
+#undef SWEEP_MNEW
+#undef SWEEP_RECORD
+#undef SWEEP_ROW_START
+#undef SWEEP_ROW_FACTOR
+}
+
+// K1bv: k_sweep_batch under per-vertex priors (sbmbp_batch_set_vertex_prior): the fourth includer of the body, with
+// k_sweep_batch's replica hooks and k_sweep_prior's row hooks over the table of replica blockIdx.y. prior_tab[r] points to the
+// table replica r reads: the batch's one shared table, the replica's own, or the batch's table of ones for a replica that holds
+// none. Shared replicas read the same lines, so the R workgroups of a segment share them in L2 as they share the segment
+// tables. The pointer is loaded where a row's line is first needed, not held in scalar registers through the kernel.
+template <int Q, bool DC2>
+__global__ void __launch_bounds__(frame_cfg<Q>::TPB) __attribute__((amdgpu_waves_per_eu(sweep_waves<Q>::N)))
+k_sweep_batch_prior(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ rev, const uint32_t *__restrict__ nbr,
+                    const uint32_t *__restrict__ ndeg /* degree of every row (DC2 only) */, const int32_t *__restrict__ clamp,
+                    const uint32_t *__restrict__ blk_row, const uint32_t *__restrict__ blk_e0, double *__restrict__ Mall, double *__restrict__ psi_all,
+                    const dev_params *__restrict__ Pall, double *__restrict__ rec_all, const int *__restrict__ par_all, size_t msg_stride,
+                    size_t psi_stride, size_t rec_stride, uint32_t j, int dc, double damp,
+                    const double *const *__restrict__ prior_tab /* [R]: tables of N*Q entries >= 0, a positive one in every row */) {
+    // (R is the grid's second dimension and is read from there: with R as one more argument beside the table, four of the
+    // thirty instantiations reserve 20 bytes of scratch, as three of k_sweep_batch's do; this way none has any)
+#define SWEEP_REPLICA                                    \
+    const uint32_t rep = blockIdx.y;                     \
+    const uint32_t R = gridDim.y;                        \
+    const dev_params *__restrict__ P = Pall + rep;       \
+    const int par = par_all[rep];
+#define SWEEP_MOLD                                       \
+    const int mc = (par + int(j)) & 1;                   \
+    const double *__restrict__ Mold = Mall + (size_t(mc) * R + rep) * msg_stride;
+#define SWEEP_PSI                                                                         \
+    const double *__restrict__ psi_old = psi_all + (size_t(mc) * R + rep) * psi_stride;  \
+    double *__restrict__ psi = psi_all + (size_t(mc ^ 1) * R + rep) * psi_stride;
+#define SWEEP_MNEW double *__restrict__ Mnew = Mall + (size_t(mc ^ 1) * R + rep) * msg_stride;
+#define SWEEP_RECORD rec_all + size_t(rep) * rec_stride + size_t(blockIdx.x) * (Q + 1)
+#define SWEEP_ROW_START(r, v) load_vec<Q>(prior_tab[rep] + size_t(r0 + uint32_t(r)) * Q, v);
+#define SWEEP_ROW_FACTOR(r, v, x) { prior_factor<Q>(prior_tab[rep] + size_t(r0 + uint32_t(r)) * Q, v, x); }
 #include "sweep_msg_body.inc"
 #undef SWEEP_REPLICA
 #undef SWEEP_MOLD
@@ -195,6 +237,7 @@ __device__ __forceinline__ double adj_pair_term(const double *__restrict__ psi, 
 // they are never live together with the row sums.
 // A hub row (a segment above CAP edges) has its site and edge terms from k_fe_hub; here its edges are walked by the whole
 // workgroup for the adjacent pairs and the numerators, and lane 0 adds its row sums.
+// The body is em_frame_body.inc, shared with the twin below; included as text, like the sweep's.
 // ------------------------------------------------------------------------------------------------
 template <int Q, bool DC2, bool EM>
 __global__ void __launch_bounds__(frame_cfg<Q>::TPB)
@@ -204,134 +247,26 @@ k_em_frame_batch(const uint32_t *__restrict__ row_ptr, const uint32_t *__restric
                  const int *__restrict__ par_all, const int *__restrict__ active, const double *__restrict__ mats_all /* [R][3 Q Q] */,
                  size_t msg_stride, size_t psi_stride, uint32_t R, int dc, int adj_mode, uint32_t rec_rows /* records per replica */,
                  double *__restrict__ partials) {
-    constexpr int EPT = frame_cfg<Q>::EPT, CAP = frame_cfg<Q>::CAP, RCAP = frame_cfg<Q>::RCAP, TPB = frame_cfg<Q>::TPB, NW = frame_cfg<Q>::WAVES;
-    constexpr int T = Q * (Q + 1) / 2, NP = em_np(Q), NRED = (EM && T > 2 * Q) ? T : 2 * Q;
-    const uint32_t rep = blockIdx.y;
-    if (!active[rep]) return;  // uniform, before any barrier
-    __shared__ double sb[CAP * Q];
-    __shared__ uint32_t srp[RCAP + 1];
-    __shared__ uint16_t srow[CAP];
-    __shared__ double sred[NW * NRED];
-    __shared__ double ssc[3];
-    const int tid = threadIdx.x;
-    const dev_params *__restrict__ P = Pall + rep;
-    const int par = par_all[rep];
-    const double *__restrict__ M = Mall + (size_t(par) * R + rep) * msg_stride;
-    const double *__restrict__ psi = psi_all + (size_t(par) * R + rep) * psi_stride;
-    const double *__restrict__ mat = mats_all + size_t(rep) * 3 * Q * Q + (adj_mode == 2 ? Q * Q : 0);
-    const double invN = P->invN;
-    const uint32_t r0 = blk_row[blockIdx.x], r1 = blk_row[blockIdx.x + 1];
-    const int nrows = int(r1 - r0);
-    const uint32_t e0 = blk_e0[blockIdx.x];
-    const int ne = int(blk_e0[blockIdx.x + 1] - e0);
-    double *__restrict__ rec = partials + (size_t(rep) * rec_rows + blockIdx.x) * NP;
-    double f_site = 0.0, f_edge = 0.0, f_adj = 0.0;
-    double tri[T];  // the numerators (lane-per-edge phase; dead without EM)
-#pragma unroll
-    for (int u = 0; u < T; ++u) tri[u] = 0.0;
-    double rs[2 * Q];  // na_expect, nna_expect (lane-per-row phase)
-#pragma unroll
-    for (int x = 0; x < 2 * Q; ++x) rs[x] = 0.0;
-    if (ne > CAP) {  // hub row (uniform)
-        const double di = double(ne);
-        for (int le = tid; le < ne; le += TPB) {
-            const uint32_t k = e0 + uint32_t(le);
-            if (EM) {
-                double mi[Q], mo[Q];
-                load_msg<Q>(M, size_t(rev[k]), mi);
-                load_msg<Q>(M, size_t(k), mo);
-                em_edge_terms<Q, DC2>(P, mi, mo, DC2 ? di * double(ndeg[nbr[k]]) : 0.0, tri);
-            }
-            if (adj_mode) f_adj += adj_pair_term<Q>(psi, r0, nbr[k], mat, invN, adj_mode);
-        }
-        if (tid == 0) {
-            double pv[Q];
-            load_vec<Q>(psi + size_t(r0) * Q, pv);
-#pragma unroll
-            for (int q = 0; q < Q; ++q) { rs[q] = pv[q]; rs[Q + q] = di * pv[q]; }
-        }
-    } else {
-        constexpr int RPT = RCAP / TPB + 1;
-        uint32_t kk[EPT], rk[EPT], rpv[RPT];
-        double mo_[EPT][Q], mi_[EPT][Q];
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) {
-            const int le = j * TPB + tid;
-            kk[j] = (ne > 0) ? e0 + uint32_t(le < ne ? le : 0) : 0u;
-        }
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) rk[j] = rev[kk[j]];
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) load_msg<Q>(M, size_t(kk[j]), mo_[j]);
-#pragma unroll
-        for (int t = 0; t < RPT; ++t) { const int r = tid + t * TPB; rpv[t] = row_ptr[r0 + uint32_t(r < nrows ? r : nrows)]; }
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) load_msg<Q>(M, size_t(rk[j]), mi_[j]);
-#pragma unroll
-        for (int t = 0; t < RPT; ++t) { const int r = tid + t * TPB; if (r <= nrows) srp[r] = rpv[t] - e0; }
-        __syncthreads();
-        if (DC2 || adj_mode) {  // uniform: per-edge weights and the adjacent pairs need the edge -> row map
-            for (int r = tid; r < nrows; r += TPB)
-                for (int e = int(srp[r]); e < int(srp[r + 1]); ++e) srow[e] = uint16_t(r);
-            __syncthreads();
-        }
-#pragma unroll
-        for (int j = 0; j < EPT; ++j) {
-            const int le = j * TPB + tid;
-            if (le < ne) {
-                double (&mi)[Q] = mi_[j];
-                double (&mo)[Q] = mo_[j];
-                double b[Q];
-                double didl = 0.0;
-                if (DC2) {
-                    const int r = srow[le];
-                    didl = double(srp[r + 1] - srp[r]) * double(ndeg[nbr[e0 + le]]);
-                }
-                edge_field<Q, DC2>(P, mi, didl, b);
-                store_vec<Q>(&sb[le * Q], b);
-                double ln, en;
-                edge_terms<Q, DC2>(P, mi, mo, didl, 0, ln, en);
-                f_edge += ln;
-                if (EM) em_edge_terms<Q, DC2>(P, mi, mo, didl, tri);
-                if (adj_mode) f_adj += adj_pair_term<Q>(psi, r0 + uint32_t(srow[le]), nbr[e0 + le], mat, invN, adj_mode);
-            }
-        }
-    }
-    // the lane-per-edge sums leave the registers here (the barriers inside also complete sb)
-    if (EM) {
-        block_sum_store<T, NW>(tri, sred, rec + EM_NA + 2 * Q);
-    } else {
-        for (int u = tid; u < T; u += TPB) rec[EM_NA + 2 * Q + u] = 0.0;  // k_em_edges_batch has them
-        __syncthreads();
-    }
-    if (ne <= CAP) {  // uniform
-        for (int r = tid; r < nrows; r += TPB) {
-            const int es = int(srp[r]), ee = int(srp[r + 1]);
-            const double di = double(ee - es);
-            double A[Q];
-            int ae[Q];
-#pragma unroll
-            for (int q = 0; q < Q; ++q) { A[q] = 1.0; ae[q] = 0; }
-            for (int e = es; e < ee; ++e) {
-#pragma unroll
-                for (int q = 0; q < Q; ++q) A[q] *= sb[e * Q + q];
-                if (((e - es) & 7) == 7) x_norm<Q>(A, ae);
-            }
-            x_norm<Q>(A, ae);
-            f_site += log_partition_x<Q>(P, dc, di, A, ae);
-            double pv[Q];
-            load_vec<Q>(psi + size_t(r0 + r) * Q, pv);
-#pragma unroll
-            for (int q = 0; q < Q; ++q) { rs[q] += pv[q]; rs[Q + q] += di * pv[q]; }
-        }
-    }
-    block_sum_store<2 * Q, NW>(rs, sred, rec + EM_NA);
-    double sc[3] = {f_site, f_edge, f_adj};
-    block_sum_store<3, NW>(sc, sred, ssc);
-    if (tid == 0) {
-        rec[0] = ssc[0]; rec[1] = ssc[1]; rec[2] = 0.0; rec[3] = 0.0; rec[4] = 0.0;
-        rec[EM_ADJ] = ssc[2];
-    }
+#define EM_SITE_FACTOR(i, v, x)
+#include "em_frame_body.inc"
+#undef EM_SITE_FACTOR
+}
+
+// K3v: k_em_frame_batch under per-vertex priors (sbmbp_batch_set_vertex_prior): the line of row i in the table of replica
+// blockIdx.y is one more factor of the product log Z_i is formed from, as in k_fe_frame_prior. A nullable table argument in
+// k_em_frame_batch itself was tried first and made it other code, so the twin: same body, other hook,
+// and k_em_frame_batch is the code it was (tools/kernel_isa_diff.py). Hub rows take k_fe_hub_prior on the replica's table.
+template <int Q, bool DC2, bool EM>
+__global__ void __launch_bounds__(frame_cfg<Q>::TPB)
+k_em_frame_batch_prior(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ rev, const uint32_t *__restrict__ nbr,
+                       const uint32_t *__restrict__ ndeg, const uint32_t *__restrict__ blk_row, const uint32_t *__restrict__ blk_e0,
+                       const double *__restrict__ Mall, const double *__restrict__ psi_all, const dev_params *__restrict__ Pall,
+                       const int *__restrict__ par_all, const int *__restrict__ active, const double *__restrict__ mats_all /* [R][3 Q Q] */,
+                       size_t msg_stride, size_t psi_stride, uint32_t R, int dc, int adj_mode, uint32_t rec_rows /* records per replica */,
+                       double *__restrict__ partials, const double *const *__restrict__ prior_tab /* [R]: the table replica r reads */) {
+#define EM_SITE_FACTOR(i, v, x) prior_factor<Q>(prior_tab[rep] + size_t(i) * Q, v, x);
+#include "em_frame_body.inc"
+#undef EM_SITE_FACTOR
 }
 
 // K5b: the EM numerators of k_em_edges for replica blockIdx.y (label counts above EM_FRAME_QMAX): grid-stride over the

@@ -1,5 +1,5 @@
-// The body of the synchronous message-gather sweep: THE definition of k_sweep, k_sweep_prior (kernels.h) and k_sweep_batch
-// (kernels_batch.h), which include this file between their braces. Not a header: no guard, no namespace, and it reads the
+// The body of the synchronous message-gather sweep: THE definition of k_sweep, k_sweep_prior (kernels.h), k_sweep_batch and
+// k_sweep_batch_prior (kernels_batch.h), which include this file between their braces. Not a header: no guard, no namespace, and it reads the
 // kernel's parameters by name:
 //     row_ptr rev nbr ndeg clamp blk_row blk_e0 dc damp          both kernels
 //     P Mold Mnew psi_old psi                                    parameters of k_sweep; the batch kernel forms them per
@@ -11,7 +11,8 @@
 //     SWEEP_MNEW      before phase 3: Mnew
 //     SWEEP_RECORD    an expression: where the segment's (Q + 1)-record goes
 //     SWEEP_ROW_START(r, v)       phase 2, lane per row: v[Q] = the factor the product of row r starts from (all ones; the
-//                                 row's prior line in k_sweep_prior), issued with the ftab line before the product loop
+//                                 row's prior line in k_sweep_prior, the line of the replica's table in
+//                                 k_sweep_batch_prior), issued with the ftab line before the product loop
 //     SWEEP_ROW_FACTOR(r, v, x)   behind a product with per-component exponents (the wave product of a row above BIG_ROW,
 //                                 the exact cavity of phase 3): one more factor into (v, x) before apply_field_x normalises
 //                                 the exponents (nothing; the row's prior line in k_sweep_prior)
