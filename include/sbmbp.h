@@ -283,8 +283,9 @@ int sbmbp_set_timing(sbmbp_engine_t *e, int on);
  * Layout in HBM (replica-major): messages [2][R][E2][Q-1], marginals [2][R][N][Q], parameter blocks [R], sweep records
  * [R][n_segments][Q+1].
  * Supported: Q = 2 .. 16, deg_corr_flag 0 / 1 / 2, zeros in cab, clamped rows, rows of any degree, damping, beta; the
- * synchronous sweep order in the message-gather form. Refused with SBMBP_ERR_UNSUPPORTED: Q > 16. A batch has no shard
- * form, no coloured sweep order and no marginal-gather form (there are no entry points that would select them).
+ * synchronous sweep order in the message-gather form and, through sbmbp_batch_set_sweep_order, the coloured order. Refused
+ * with SBMBP_ERR_UNSUPPORTED: Q > 16. A batch has no shard form and no marginal-gather form (there are no entry points
+ * that would select them).
  * SBMBP_ERR_ARG: n_replicas = 0 or above 65535 (the replica is the second grid dimension), Q < 2, a replica index >= R.
  * SBMBP_ERR_NOMEM: R (2 E2 (Q-1) + 2 N Q) 8 bytes of state do not fit the free HBM. Argument errors are reported before
  * any device work; without a GPU the call returns SBMBP_ERR_NODEVICE as sbmbp_create does.
@@ -342,6 +343,24 @@ int sbmbp_batch_get_relaxation(const sbmbp_batch_t *b, uint32_t replica, int *fi
 int sbmbp_batch_set_schedule(sbmbp_batch_t *b, double field_mix, uint32_t check_every);
 int sbmbp_batch_set_auto_relax(sbmbp_batch_t *b, int on);
 int sbmbp_batch_set_nonedge_mode(sbmbp_batch_t *b, int nonedge_mode, int series_order);
+/* Sweep order of the batch, common to all replicas (the colouring and the step tables belong to the graph). The arguments
+ * mean what sbmbp_set_sweep_order's mean: order 0 = synchronous (default), 1 = coloured Gauss-Seidel; colour NULL = the
+ * built-in greedy colouring, else N entries, validated; step_fraction 0 = default 1/8. The plan and the device tables are the
+ * single engine's. Under order 1 sbmbp_batch_sweep / _converge / _inference / _em_step / _learning advance every replica by
+ * the coloured launch sequence: per step one launch over (segments of the step, R) and one fold-and-update launch with a
+ * workgroup per replica, plus the hub pair of every replica in steps that hold rows above a segment's capacity. Replica r
+ * goes through the states of a single engine in the same order with the same step_fraction: in place on the buffer that
+ * holds its state, so its stopping sweep, niter[r], last_maxdiff[r] (the maximum over the steps of the undamped 1-step
+ * difference) and state are its own. No relaxation of any kind: sbmbp_batch_get_relaxation reports (0, -1, 1, 1) for every
+ * replica while the order is 1; field_mix of sbmbp_batch_set_schedule / sbmbp_batch_set_learning_schedule and
+ * sbmbp_batch_set_auto_relax are ignored; damping is honoured. Switching the order keeps every replica's state; going back to
+ * order 0 keeps the tables. The sweep records of a replica grow to max(n_segments, records of the largest step) (Q + 1)
+ * doubles when order 1 is set.
+ * SBMBP_ERR_UNSUPPORTED: order 1 while a replica holds a per-vertex prior, and sbmbp_batch_set_vertex_prior with a table
+ * while the order is 1 (the step kernels take no prior). SBMBP_ERR_ARG: b NULL, an order other than 0 / 1, an invalid
+ * colouring. sbmbp_batch_get_sweep_order: as sbmbp_get_sweep_order (n_colours = n_steps = 0 under order 0). */
+int sbmbp_batch_set_sweep_order(sbmbp_batch_t *b, int order, const uint32_t *colour, double step_fraction);
+int sbmbp_batch_get_sweep_order(const sbmbp_batch_t *b, int *order, uint32_t *n_colours, uint32_t *n_steps);
 /* exactly n_sweeps sweeps of every replica (never relaxed); last_maxdiff: R entries or NULL */
 int sbmbp_batch_sweep(sbmbp_batch_t *b, double damping, uint32_t n_sweeps, double *last_maxdiff);
 /* niter[r] / last_maxdiff[r]: sbmbp_converge's meaning for replica r alone. The call ends when every replica has stopped

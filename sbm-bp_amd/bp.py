@@ -428,7 +428,7 @@ class bp_conditional(BeliefPropagation):
 class ReplicaBatch:
     """R independent BP runs over one graph in one launch sequence per sweep (sbmbp.h: sbmbp_batch_*). Every replica has its
     own initial state, its own (cab, na, beta) and its own convergence and relaxation state; arrays over replicas have
-    shape [R, ...]. Q = 2 .. 16, synchronous sweeps in the message-gather form."""
+    shape [R, ...]. Q = 2 .. 16, synchronous sweeps in the message-gather form, or coloured sweeps (set_sweep_order)."""
 
     def __init__(self, graph, Q, deg_corr_flag=0, n_replicas=1, device=-1):
         self._lib = load_library()
@@ -552,6 +552,27 @@ class ReplicaBatch:
 
     def set_nonedge_mode(self, mode=0, series_order=0):
         check(self._lib.sbmbp_batch_set_nonedge_mode(self._h, mode, series_order))
+
+    def set_sweep_order(self, order="coloured", colour=None, step_fraction=0):
+        """the sweep order of all replicas, as BeliefPropagation.set_sweep_order takes it: "jacobi" / 0 = synchronous (default),
+        "coloured" / 1 = coloured Gauss-Seidel sweeps with the field refreshed inside a sweep (sbmbp.h
+        sbmbp_batch_set_sweep_order). colour=None: built-in greedy colouring; step_fraction 0 = 1/8. Every replica keeps its state"""
+        code = {"jacobi": 0, "coloured": 1}.get(order, order)
+        cin = None
+        if colour is not None:
+            cin = np.ascontiguousarray(colour, dtype=np.uint32)
+            if len(cin) != self.N:
+                raise ValueError("colour needs N entries")
+        check(self._lib.sbmbp_batch_set_sweep_order(self._h, int(code), None if cin is None else cin.ctypes.data_as(c_u32p),
+                                                    float(step_fraction)))
+
+    @property
+    def sweep_order(self):
+        """(order, n_colours, n_steps), the tuple BeliefPropagation.sweep_order() returns: order 0 = synchronous (the counts
+        are 0), 1 = coloured"""
+        o, nc, ns = C.c_int(0), C.c_uint32(0), C.c_uint32(0)
+        check(self._lib.sbmbp_batch_get_sweep_order(self._h, C.byref(o), C.byref(nc), C.byref(ns)))
+        return o.value, nc.value, ns.value
 
     # -- hot path ---------------------------------------------------------------------------
     def sweep(self, n_sweeps=1, dumping_rate=1.0):

@@ -132,6 +132,8 @@ SYMBOLS = {
     "sbmbp_batch_set_schedule": (C.c_int, [C.c_void_p, C.c_double, C.c_uint32]),
     "sbmbp_batch_set_auto_relax": (C.c_int, [C.c_void_p, C.c_int]),
     "sbmbp_batch_set_nonedge_mode": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "sbmbp_batch_set_sweep_order": (C.c_int, [C.c_void_p, C.c_int, c_u32p, C.c_double]),
+    "sbmbp_batch_get_sweep_order": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_u32p, c_u32p]),
     "sbmbp_batch_sweep": (C.c_int, [C.c_void_p, C.c_double, C.c_uint32, c_dp]),
     "sbmbp_batch_converge": (C.c_int, [C.c_void_p, C.c_double, C.c_uint32, C.c_double, C.POINTER(C.c_int), c_dp]),
     "sbmbp_batch_free_energy": (C.c_int, [C.c_void_p, c_dp, c_dp]),

@@ -357,7 +357,7 @@ int main(int argc, char const *argv[]) {
         if (restarts < 1) conflict = "--restarts needs a value of at least 1";
         else if (mode == "learn") conflict = "--restarts cannot be combined with -m learn (restarts are runs of -m infer)";
         else if (n_gpus > 1) conflict = "--restarts cannot be combined with --gpus above 1 (a replica batch runs on one GPU)";
-        else if (schedule == "coloured") conflict = "--restarts cannot be combined with --schedule coloured (a replica batch sweeps synchronously)";
+        else if (schedule == "coloured") conflict = "--restarts cannot be combined with --schedule coloured (the command line runs a replica batch synchronously; its coloured order is sbmbp_batch_set_sweep_order in C, ReplicaBatch.set_sweep_order in Python)";
         else if (Q > 16) conflict = "--restarts cannot be combined with more than 16 blocks (Q > 16)";
         if (conflict) { std::clog << "bp: " << conflict << "\n"; return 1; }
     }
@@ -368,7 +368,7 @@ int main(int argc, char const *argv[]) {
         if (lrestarts < 1) conflict = "--learn_restarts needs a value of at least 1";
         else if (mode == "infer") conflict = "--learn_restarts cannot be combined with -m infer (they are runs of -m learn; -m infer has --restarts)";
         else if (n_gpus > 1) conflict = "--learn_restarts cannot be combined with --gpus above 1 (a replica batch runs on one GPU)";
-        else if (schedule == "coloured") conflict = "--learn_restarts cannot be combined with --schedule coloured (a replica batch sweeps synchronously)";
+        else if (schedule == "coloured") conflict = "--learn_restarts cannot be combined with --schedule coloured (the command line runs a replica batch synchronously; its coloured order is sbmbp_batch_set_sweep_order in C, ReplicaBatch.set_sweep_order in Python)";
         else if (Q > 16) conflict = "--learn_restarts cannot be combined with more than 16 blocks (Q > 16)";
         if (conflict) { std::clog << "bp: " << conflict << "\n"; return 1; }
     }

@@ -2337,6 +2337,7 @@ struct batch_replica {
     int ar_fl = 0, ar_gl = -1;  // levels the last converge call ended on
     int prior_state = 0;        // per-vertex prior (sbmbp_batch_set_vertex_prior): 0 = none, 1 = the batch's shared table, 2 = own
     double *d_prior = nullptr;  // the own table [N*Q] (state 2)
+    bool cs_last = false;       // the replica's last sweeps ran in the coloured order (sbmbp_engine::cs_last, per replica)
 };
 struct sbmbp_batch {
     sbmbp_engine *e = nullptr;
@@ -2392,6 +2393,7 @@ struct bound_replica {
         e->cab = p.cab; e->eta = p.eta; e->na = p.na; e->beta = p.beta;
         e->have_params = p.have_params; e->have_state = p.have_state; e->field_fresh = p.field_fresh; e->w_positive = p.w_positive;
         e->ar_fl = p.ar_fl; e->ar_gl = p.ar_gl;
+        e->cs_last = p.cs_last;
         e->psi_consistent = false; e->init_from_psi = false; e->fz.valid = false;  // message-gather form only
     }
     ~bound_replica() {
@@ -2403,6 +2405,7 @@ struct bound_replica {
         e->d_M[0] = e->d_M[1] = e->d_psi[0] = e->d_psi[1] = nullptr;
         e->d_P = nullptr;
         e->d_prior = nullptr;  // the tables are the batch's
+        e->cs_last = false;
         e->have_state = e->have_params = false;
     }
 };
@@ -2455,6 +2458,38 @@ int batch_launch_sweep(sbmbp_batch *b, const batch_view &bv, uint32_t j, double 
     return SBMBP_OK;
 }
 
+// One sweep of the coloured order for all replicas (launch_coloured_sweep with the replica as the grid's second dimension):
+// per step the hub pair of every replica (the single engine's kernels on offset pointers, over the step-ordered fragment
+// tables; the fragment scratch is shared, and the launches of one replica follow each other in the one stream), ONE
+// k_sweep_step_batch and ONE k_step_finalize_batch, all in place on the buffer call_par[r] of every replica.
+int batch_launch_coloured_sweep(sbmbp_batch *b, const batch_view &bv, double damp) {
+    sbmbp_engine *e = b->e;
+    const int32_t *clamp = e->has_clamp ? e->d_clamp : nullptr;
+    const hub_frags hf{e->d_cs_frag_hub, e->d_cs_hub_frag0, e->d_hub_b, e->d_hub_pA, e->d_hub_pE};
+    for (uint32_t s = 0; s < e->cs_steps; ++s) {
+        const uint32_t seg0 = e->cs_seg0[s], nseg = e->cs_seg0[s + 1] - seg0, nh = e->cs_hub0[s + 1] - e->cs_hub0[s];
+        if (nh) {
+            const uint32_t f0 = e->cs_frag0[s], nf = e->cs_frag0[s + 1] - f0;
+            for (uint32_t r = 0; r < b->R; ++r) {
+                double *M = bv.M + (size_t(b->call_par[r]) * b->R + r) * bv.msg_stride, *psi = bv.psi + (size_t(b->call_par[r]) * b->R + r) * bv.psi_stride;
+                double *rec = bv.rec + size_t(r) * bv.rec_stride;
+                DISPATCH_QB(e->Q, e->dc == 2, hipLaunchKernelGGL((k_hub_frag_product_msg<QQ, BB>), dim3(nf), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev,
+                                                                 e->d_nbr, e->d_deg, M, e->d_cs_hub_row, e->d_cs_hub_rec, hf, f0, bv.P + r, rec, clamp));
+                DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_step_cavity<QQ>), dim3(nf), dim3(BLOCK), 0, e->stream, e->d_row_ptr, M, psi, e->d_cs_hub_row,
+                                                    e->d_cs_hub_rec, hf, f0, bv.P + r, int(e->dc != 0), damp, rec, clamp));
+            }
+        }
+        if (nseg)
+            DISPATCH_QB(e->Q, e->dc == 2, hipLaunchKernelGGL((k_sweep_step_batch<QQ, BB>), dim3(nseg, b->R), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
+                                                             e->d_rev, e->d_nbr, e->d_deg, bv.M, bv.psi, clamp, e->d_cs_rows, e->d_cs_loff, e->d_cs_seg_row0, seg0,
+                                                             bv.P, bv.par, bv.msg_stride, bv.psi_stride, bv.rec_stride, int(e->dc != 0), damp, bv.rec));
+        DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_step_finalize_batch<QQ>), dim3(b->R), dim3(BLOCK), 0, e->stream, bv.P, bv.rec, bv.rec_stride, nseg + nh,
+                                            int(s + 1 == e->cs_steps)));
+    }
+    HIPCHK(hipGetLastError());
+    return SBMBP_OK;
+}
+
 int batch_check_ready(const sbmbp_batch *b, const char *what) {
     for (uint32_t r = 0; r < b->R; ++r)
         if (!b->rep[r].have_params || !b->rep[r].have_state) {
@@ -2468,12 +2503,15 @@ int batch_check_ready(const sbmbp_batch *b, const char *what) {
 // crit[r] is replica r's criterion. active (null = all): a replica that is not active is frozen: its parameter block is not
 // uploaded again, its stop flag is set, and its state and parity stay untouched; executed[r] (may be null) = sweeps replica
 // r executed in this call.
+// In the coloured order (sbmbp_batch_set_sweep_order) the sweeps of the call are batch_launch_coloured_sweep's: in place, so
+// no replica's parity moves, and without relaxation of any kind (step_update), as run_sweeps_coloured on the single engine.
 int batch_run(sbmbp_batch *b, const double *crit, const uint8_t *active, uint32_t max_sweeps, double damping, int *niter, double *last,
               uint32_t *executed_out = nullptr) {
     sbmbp_engine *e = b->e;
     const uint32_t R = b->R;
     CHK(batch_check_ready(b, "converge"));
     CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (e->Q + 1)));
+    const bool coloured = e->sweep_order == 1;
     b->call_par.resize(R);
     for (uint32_t r = 0; r < R; ++r) {  // parameter block and initial field of every replica (once per call: a loop)
         b->call_par[r] = b->rep[r].par;
@@ -2496,7 +2534,7 @@ int batch_run(sbmbp_batch *b, const double *crit, const uint8_t *active, uint32_
     // batches are queued one ahead, as in run_sweeps: the GPU never idles while the host reads the states
     auto queue_batch = [&](int slot) -> int {
         const uint32_t n = std::min(batch_max, max_sweeps - done);
-        for (uint32_t k = 0; k < n; ++k) CHK(batch_launch_sweep(b, bv, done + k, damping));
+        for (uint32_t k = 0; k < n; ++k) CHK(coloured ? batch_launch_coloured_sweep(b, bv, damping) : batch_launch_sweep(b, bv, done + k, damping));
         done += n;
         constexpr uint32_t words = sizeof(conv_state) / 4;
         hipLaunchKernelGGL(k_batch_conv_states, dim3(std::min<uint32_t>(64, (R * words + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, e->stream, b->d_P, R,
@@ -2519,12 +2557,19 @@ int batch_run(sbmbp_batch *b, const double *crit, const uint8_t *active, uint32_
         batch_replica &p = b->rep[r];
         const uint32_t executed = uint32_t(cs[r].sweep_idx);
         if (executed_out) executed_out[r] = executed;
-        p.par = (p.par + int(executed)) & 1;
         b->sweeps += executed;
-        const bool relaxed = cs[r].ar_fl > 0 || cs[r].ar_gl >= 0;
-        p.field_fresh = (e->field_mix >= 1.0) && !relaxed && executed > 0;
-        p.ar_fl = cs[r].ar_fl;
-        p.ar_gl = cs[r].ar_gl;
+        p.cs_last = coloured;
+        if (coloured) {  // in place: the parity stays; the field followed the marginals step by step (run_sweeps_coloured)
+            p.field_fresh = true;
+            p.ar_fl = 0;
+            p.ar_gl = -1;
+        } else {
+            p.par = (p.par + int(executed)) & 1;
+            const bool relaxed = cs[r].ar_fl > 0 || cs[r].ar_gl >= 0;
+            p.field_fresh = (e->field_mix >= 1.0) && !relaxed && executed > 0;
+            p.ar_fl = cs[r].ar_fl;
+            p.ar_gl = cs[r].ar_gl;
+        }
         if (niter) niter[r] = cs[r].conv_iter;
         if (last) last[r] = cs[r].maxdiff;  // message-gather sweeps report the 1-step difference
     }
@@ -2832,6 +2877,10 @@ int sbmbp_batch_set_vertex_prior(sbmbp_batch_t *b, int replica, const double *pr
     sbmbp_engine *e = b->e;
     const uint32_t R = b->R;
     const size_t n = size_t(e->N) * e->Q;
+    if (prior && e->sweep_order == 1) {
+        set_error("a per-vertex prior cannot be combined with the coloured sweep order: sbmbp_batch_set_sweep_order(b, 0, ...) first");
+        return SBMBP_ERR_UNSUPPORTED;
+    }
     if (prior) {
         std::string why;
         const uint32_t bad = first_bad_prior_row(prior, e->N, e->Q, &why);
@@ -2913,6 +2962,13 @@ int sbmbp_batch_get_relaxation(const sbmbp_batch_t *b, uint32_t replica, int *fi
     BATCH_ARGS(b);
     CHK(batch_replica_arg(b, replica));
     const batch_replica &p = b->rep[replica];
+    if (b->e->sweep_order == 1) {  // no relaxation of any kind in the coloured order
+        if (field_level) *field_level = 0;
+        if (generic_level) *generic_level = -1;
+        if (field_mix) *field_mix = 1.0;
+        if (damping_factor) *damping_factor = 1.0;
+        return SBMBP_OK;
+    }
     if (field_level) *field_level = p.ar_fl;
     if (generic_level) *generic_level = p.ar_gl;
     if (field_mix) *field_mix = std::min(std::min(b->e->field_mix, ar_field_cap(p.ar_fl)), ar_gen_mix(p.ar_gl));
@@ -2931,6 +2987,41 @@ int sbmbp_batch_set_auto_relax(sbmbp_batch_t *b, int on) {
 int sbmbp_batch_set_nonedge_mode(sbmbp_batch_t *b, int nonedge_mode, int series_order) {
     BATCH_ARGS(b);
     return sbmbp_set_nonedge_mode(b->e, nonedge_mode, series_order);
+}
+
+// The order is common to all replicas: the colouring and the step tables belong to the graph, and they are the single
+// engine's (sbmbp_set_sweep_order on the batch's engine: coloured_plan, coloured_step_tables, build_coloured). A step's
+// records are (Q + 1) doubles per segment and hub row of the step, so the record table of every replica grows to
+// max(n_blk, cs_max_rec) records here; going back to order 0 keeps tables and records (a later switch is cheap, and the
+// synchronous sweep reads the stride it is given).
+int sbmbp_batch_set_sweep_order(sbmbp_batch_t *b, int order, const uint32_t *colour, double step_fraction) {
+    if (!b || order < 0 || order > 1) return arg_error(__func__, __LINE__);
+    sbmbp_engine *e = b->e;
+    device_scope dev_(e);
+    if (order == 1 && b->n_prior) {
+        set_error("the coloured sweep order takes no per-vertex prior: remove it first (sbmbp_batch_set_vertex_prior(b, -1, NULL))");
+        return SBMBP_ERR_UNSUPPORTED;
+    }
+    CHK(sbmbp_set_sweep_order(e, order, colour, step_fraction));
+    if (order == 0) return SBMBP_OK;
+    const size_t need = size_t(std::max<uint32_t>(std::max(e->n_blk, e->cs_max_rec), 1)) * (e->Q + 1);
+    if (need > b->rec_stride) {
+        HIPCHK(hipStreamSynchronize(e->stream));  // nothing in flight writes the records that are freed
+        double *rec = nullptr;
+        const int r = dev_alloc(e, &rec, size_t(b->R) * need);
+        if (r != SBMBP_OK) { e->sweep_order = 0; return r; }
+        (void)hipFree(b->d_rec);
+        e->device_bytes -= size_t(b->R) * b->rec_stride * 8;
+        b->d_rec = rec;
+        b->rec_stride = need;
+        HIPCHK(hipMemsetAsync(b->d_rec, 0, size_t(b->R) * need * 8, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    return SBMBP_OK;
+}
+int sbmbp_batch_get_sweep_order(const sbmbp_batch_t *b, int *order, uint32_t *n_colours, uint32_t *n_steps) {
+    BATCH_ARGS(b);
+    return sbmbp_get_sweep_order(b->e, order, n_colours, n_steps);
 }
 
 int sbmbp_batch_sweep(sbmbp_batch_t *b, double damping, uint32_t n_sweeps, double *last) {

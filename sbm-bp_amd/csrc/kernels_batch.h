@@ -12,6 +12,9 @@
 // The same holds below the sweep: every batch kernel here is the replica's addressing, a call of the single engine's
 // __device__ rule in kernels.h (finalize_update, psi_row_add, em_edge_terms, moments_chunk, nonedge_pair_sums) and its
 // own final store. The stores stay apart because block_sum_store and block_reduce_store fold in different orders.
+// The coloured sweep order (sbmbp_batch_set_sweep_order) has the same shape: k_sweep_step_batch includes sweep_step_body.inc,
+// the body of k_sweep_step, and k_step_finalize_batch calls step_update; the records are then [R][max(n_segments, records of
+// the largest step)][Q+1].
 // Per-vertex priors (sbmbp_batch_set_vertex_prior): k_sweep_batch_prior and k_em_frame_batch_prior are the twins of the two
 // kernels whose row products a prior line enters, over the same bodies; they find the table of replica r in prior_tab[r].
 #ifndef SBMBP_KERNELS_BATCH_H
@@ -128,6 +131,56 @@ k_finalize_batch(dev_params *__restrict__ Pall, const double *__restrict__ rec_a
     __shared__ double s_hN[Q];
     fold_rows<Q, false>(rec_all + size_t(blockIdx.x) * rec_stride, 0, n_rec, sacc, sout);
     if (threadIdx.x == 0) finalize_update<Q>(P, sout, 0, nullptr, 0u, 1, s_hN);
+    __syncthreads();
+    field_table<Q>(P, s_hN);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Coloured sweep order in a batch (sbmbp_batch_set_sweep_order). The colouring and the step tables belong to the graph, so
+// all replicas walk the same steps; a step is ONE launch over (segments of the step, R).
+// K1sb: k_sweep_step over segment seg_base + blockIdx.x of replica blockIdx.y, in place on the buffer that holds the
+// replica's current state, par[r]: the coloured order never alternates buffers, so no sweep number enters the address and
+// the host leaves the parity where it was. The body is sweep_step_body.inc, shared with k_sweep_step; M and psi are formed
+// per replica where they are first needed, unqualified as there (read and written). R is the grid's second dimension and is
+// read from there (see k_sweep_batch_prior). A stopped replica returns before any barrier and nothing of its state is touched.
+// The replica's slot par[r] R + r is formed ONCE, at the top: with the parity loaded again at each of the two places that
+// need it the kernel took 2 - 3 more vector registers than k_sweep_step from Q = 9 on (scalar registers spilled into them)
+// and Q = 16 reserved 12 / 32 bytes of scratch where k_sweep_step has none (tools/kernel_resources.py).
+// ------------------------------------------------------------------------------------------------
+template <int Q, bool DC2>
+__global__ void __launch_bounds__(frame_cfg<Q>::TPB) __attribute__((amdgpu_waves_per_eu(sweep_waves<Q>::N)))
+k_sweep_step_batch(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ rev, const uint32_t *__restrict__ nbr,
+                   const uint32_t *__restrict__ ndeg /* degree of every row (DC2 only) */, double *Mall, double *psi_all,
+                   const int32_t *__restrict__ clamp, const uint32_t *__restrict__ rows, const uint32_t *__restrict__ loff,
+                   const uint32_t *__restrict__ seg_row0, uint32_t seg_base, const dev_params *__restrict__ Pall,
+                   const int *__restrict__ par_all, size_t msg_stride, size_t psi_stride, size_t rec_stride, int dc, double damp,
+                   double *__restrict__ rec_all) {
+#define STEP_REPLICA                                     \
+    const uint32_t rep = blockIdx.y;                     \
+    const dev_params *__restrict__ P = Pall + rep;       \
+    const size_t slot = size_t(par_all[rep]) * gridDim.y + rep;
+#define STEP_M double *M = Mall + slot * msg_stride;
+#define STEP_PSI double *psi = psi_all + slot * psi_stride;
+#define STEP_RECORD rec_all + size_t(rep) * rec_stride + size_t(blockIdx.x) * (Q + 1)
+#include "sweep_step_body.inc"
+#undef STEP_REPLICA
+#undef STEP_M
+#undef STEP_PSI
+#undef STEP_RECORD
+}
+
+// K2sb: workgroup r folds replica r's n_rec records of the step in k_step_finalize's order and runs step_update on P[r]:
+// every replica carries its own cs_md, maxdiff, conv_iter, sweep_idx and stop flag (no difference history in a batch)
+template <int Q>
+__global__ void __launch_bounds__(BLOCK)
+k_step_finalize_batch(dev_params *__restrict__ Pall, const double *__restrict__ rec_all, size_t rec_stride, uint32_t n_rec, int last_step) {
+    dev_params *__restrict__ P = Pall + blockIdx.x;
+    if (P->stop) return;
+    __shared__ double sacc[(BLOCK / 64) * (Q + 1)];
+    __shared__ double sout[Q + 1];
+    __shared__ double s_hN[Q];
+    fold_rows<Q, false>(rec_all + size_t(blockIdx.x) * rec_stride, 0, n_rec, sacc, sout);
+    if (threadIdx.x == 0) step_update<Q>(P, sout, last_step, nullptr, 0u, s_hN);
     __syncthreads();
     field_table<Q>(P, s_hN);
 }
