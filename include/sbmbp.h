@@ -397,6 +397,41 @@ int sbmbp_batch_em_step(sbmbp_batch_t *b, double *na_expect, double *nna_expect,
 int sbmbp_batch_learning(sbmbp_batch_t *b, float learning_conv_crit, uint32_t learning_max_time, float learning_rate,
                          float dumping_rate, sbmbp_learn_result *out, double *eta, double *cab, uint32_t *best);
 
+/* Agreement of replicas: how many different fixed points the starts of a batch found, which replicas are the same state up
+ * to a relabelling of the groups, and whether the best run is an outlier. No reference counterpart.
+ * A call takes a list of n replicas x = 0 .. n-1 of the batch; replicas == NULL means all R in index order.
+ *   psi^x_i  = the marginal row of vertex i that sbmbp_batch_get_state(b, replicas[x], psi, NULL) would return at the time of the
+ *              call: the table of the replica's current parity, in whichever sweep order it last ran, with or without priors
+ *   l^x_i    = the label of the largest entry of that row; ties go to the lowest index, a NaN never wins, a row of NaNs gives 0
+ * For every ordered pair (x, y) the Q x Q confusion matrix, by kind:
+ *   SBMBP_AGREE_SOFT       C_xy[a][b] = sum_i psi^x_i[a] psi^y_i[b]
+ *   SBMBP_AGREE_HARD_SOFT  C_xy[a][b] = sum_{i : l^x_i = a} psi^y_i[b]: compute_overlap's confusion (sbmbp_confusion) with the
+ *                          labels of replica x as the true configuration
+ *   SBMBP_AGREE_HARD       C_xy[a][b] = #{ i : l^x_i = a and l^y_i = b }: symmetric, exact (integer sums), overlap_xx = 1
+ *   overlap_xy = max over ALL permutations pi of sum_a C_xy[a][pi(a)] / N, and perm_xy a maximising pi: label a of x
+ *                corresponds to label pi(a) of y. Exact for every Q (maximum-weight assignment on the host, O(Q^3)); the
+ *                identity rule above Q = 8 belongs to sbmbp_overlap, the overlap with the true configuration, which is unchanged.
+ * The confusion matrices are ONE Gram matrix over the marginal tables where they lie in HBM (csrc/kernels_batch.h: k_agree, on
+ * the matrix cores), folded without atomics: two calls return the same bits. The call reads the marginals and changes nothing:
+ * not a replica's state, parity, stop flag or cached flags, no statistic (the buffers it allocates on first need are not in
+ * device_bytes), not the engine's binding. It runs on the batch's stream behind whatever is queued.
+ * Refused before any device work: SBMBP_ERR_ARG for a null batch, a kind outside 0 .. 2, n = 0 with a list, a listed replica
+ * >= R or listed twice; SBMBP_ERR_UNSUPPORTED for n Q > 256 (pass a subset list); SBMBP_ERR_STATE for a listed replica
+ * without a state.
+ * sbmbp_agreement_groups: host only, no device. Replicas in ascending order: x joins the group of the FIRST earlier group leader
+ * g with overlap[g n + x] >= threshold, else x becomes the leader of a new group; group[x] = the group's number in order of
+ * creation. Deterministic, no linkage beyond the leaders (0-1 and 1-2 above the threshold and 0-2 below it: 2 leads a group).
+ * Meant for kind HARD, where the overlap of a replica with itself is 1; any matrix is accepted. */
+#define SBMBP_AGREE_SOFT 0
+#define SBMBP_AGREE_HARD_SOFT 1
+#define SBMBP_AGREE_HARD 2
+int sbmbp_batch_agreement(sbmbp_batch_t *b, int kind, const uint32_t *replicas /* n, or NULL = all R */, uint32_t n,
+                          double *confusion /* n*n*Q*Q: [((x*n + y)*Q + a)*Q + b], or NULL */,
+                          double *overlap   /* n*n, or NULL */,
+                          uint32_t *perm    /* n*n*Q: [(x*n + y)*Q + a] = pi(a), or NULL */);
+int sbmbp_agreement_groups(uint32_t n, const double *overlap /* n*n */, double threshold,
+                           uint32_t *group /* n */, uint32_t *n_groups);
+
 /* ---------------------------------------------------------------------------------------------
  * Vertex-range sharding: the per-shard STEPS (one engine per GPU). No reference counterpart: the
  * reference is single-process. A shard owns a contiguous range of rows, their out-messages and

@@ -12,7 +12,7 @@ compiled library and a GPU and fails loudly otherwise.
 from sbm_bp_amd.build import build_all, lib_path  # noqa: F401
 from sbm_bp_amd.capi import SbmbpError, load_library  # noqa: F401
 from sbm_bp_amd.bp import (  # noqa: F401
-    BeliefPropagation, Graph, ReplicaBatch, blockmodel_t, bp_basic, bp_blockmodel_state, bp_conditional, bp_param_from_direct,
+    BeliefPropagation, Graph, ReplicaBatch, agreement_groups, blockmodel_t, bp_basic, bp_blockmodel_state, bp_conditional, bp_param_from_direct,
     bp_param_from_epsilon_c, coloured_plan, format_infer_line, load_beliefs, load_confs, load_edge_list,
     load_priors,
 )

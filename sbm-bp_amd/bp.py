@@ -644,6 +644,50 @@ class ReplicaBatch:
         check(self._lib.sbmbp_batch_get_stats(self._h, C.byref(s)))
         return s
 
+    # -- agreement of the replicas (sbmbp.h sbmbp_batch_agreement) --------------------------------
+    def agreement(self, kind="hard", replicas=None):
+        """pairwise agreement of the listed replicas (None = all R, in index order): (overlap[n, n], confusion[n, n, Q, Q],
+        perm[n, n, Q]). kind "soft" / "hard_soft" / "hard" (or 0 / 1 / 2) selects the confusion matrix; overlap[x, y] is its
+        best trace / N over ALL relabellings and perm[x, y, a] the label of y that label a of x corresponds to. Reads the
+        marginals where they lie on the device and changes nothing."""
+        k = AGREEMENT_KINDS[kind] if isinstance(kind, str) else int(kind)
+        lst = None
+        n = self.R
+        if replicas is not None:
+            lst = np.ascontiguousarray(replicas, dtype=np.uint32).ravel()
+            n = len(lst)
+            if n == 0:  # an empty list is refused by the library, which needs a pointer that is not NULL to tell it from "all"
+                lst = np.zeros(1, dtype=np.uint32)
+        Q = self.Q
+        conf = np.zeros((n, n, Q, Q))
+        ov = np.zeros((n, n))
+        perm = np.zeros((n, n, Q), dtype=np.uint32)
+        check(self._lib.sbmbp_batch_agreement(self._h, k, None if lst is None else lst.ctypes.data_as(c_u32p), n, _dp(conf), _dp(ov),
+                                              perm.ctypes.data_as(c_u32p)))
+        return ov, conf, perm
+
+    def agreement_groups(self, threshold, kind="hard", replicas=None):
+        """(group[n], n_groups, overlap): the groups of agreement_groups() on the overlap matrix of agreement(kind, replicas)"""
+        ov = self.agreement(kind, replicas)[0]
+        group, n_groups = agreement_groups(ov, threshold)
+        return group, n_groups, ov
+
+
+AGREEMENT_KINDS = {"soft": 0, "hard_soft": 1, "hard": 2}
+
+
+def agreement_groups(overlap, threshold):
+    """groups of runs from an n x n overlap matrix (sbmbp.h sbmbp_agreement_groups; host only, no GPU): run x joins the group of
+    the first earlier group leader g with overlap[g, x] >= threshold, else it leads a new group. Returns (group[n], n_groups)."""
+    ov = np.ascontiguousarray(overlap, dtype=np.float64)
+    if ov.ndim != 2 or ov.shape[0] != ov.shape[1]:
+        raise ValueError("overlap must be a square matrix")
+    n = ov.shape[0]
+    group = np.zeros(n, dtype=np.uint32)
+    ng = C.c_uint32(0)
+    check(load_library().sbmbp_agreement_groups(n, _dp(ov), float(threshold), group.ctypes.data_as(c_u32p), C.byref(ng)))
+    return group, ng.value
+
 
 def format_infer_line(res):
     """the stdout line of belief_propagation.cpp:88 at the default 6 significant digits"""

@@ -147,6 +147,8 @@ SYMBOLS = {
     "sbmbp_batch_learning": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_float, C.c_float, C.POINTER(LearnResult), c_dp, c_dp, c_u32p]),
     "sbmbp_learning_step_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, c_dp, c_dp, c_u32p, c_dp]),
     "sbmbp_best_replica": (C.c_int, [C.c_uint32, c_dp, C.POINTER(C.c_int), C.c_int, c_u32p]),
+    "sbmbp_batch_agreement": (C.c_int, [C.c_void_p, C.c_int, c_u32p, C.c_uint32, c_dp, c_dp, c_u32p]),
+    "sbmbp_agreement_groups": (C.c_int, [C.c_uint32, c_dp, C.c_double, c_u32p, c_u32p]),
     # shard steps (sbm-bp_amd/distributed.py); desc/state structs are declared there
     "sbmbp_shard_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(ShardDesc), C.c_uint32, C.c_uint32, C.c_int]),
     "sbmbp_shard_begin": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),

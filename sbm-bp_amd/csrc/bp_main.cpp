@@ -10,6 +10,7 @@
 // this node, one host thread per GPU driving the C++ multi-GPU driver (sbmbp_dist_*, RCCL over xGMI); with fewer devices
 // than ranks the ranks share devices over the in-process transport (a rehearsal, not a speed-up). --prior_path FILE: per-vertex
 // label priors (sbmbp_set_vertex_prior; single GPU, jacobi, up to 16 blocks), -m infer and -m learn.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -43,7 +44,7 @@ const opt_spec OPTS[] = {
     // extensions
     {"precision", 0, 1}, {"device", 0, 1}, {"gather", 0, 1}, {"field_mix", 0, 1}, {"check_every", 0, 1}, {"metrics_json", 0, 1},
     {"gpus", 0, 1}, {"transport", 0, 1}, {"schedule", 0, 1}, {"step_fraction", 0, 1}, {"restarts", 0, 1},
-    {"learn_restarts", 0, 1}, {"prior_path", 0, 1},
+    {"learn_restarts", 0, 1}, {"prior_path", 0, 1}, {"agreement", 0, 1},
 };
 
 const opt_spec *find_long(const std::string &name) {
@@ -172,7 +173,40 @@ void usage(const char *argv0) {
                  "  --prior_path arg      per-vertex label priors: text, one line 'vertex w_0 ... w_{Q-1}' per annotated vertex, any order,\n"
                  "                        weights >= 0 with a positive one per line; vertices not listed have no prior. A vertex's weights\n"
                  "                        multiply the group prior in its marginal and its messages (-m infer and -m learn; single GPU,\n"
-                 "                        jacobi, up to 16 blocks)\n";
+                 "                        jacobi, up to 16 blocks)\n"
+                 "  --agreement arg       with --restarts R / --learn_restarts R above 1: after the runs, the pairwise agreement of all R\n"
+                 "                        final states (overlap of their most likely labels, best over all relabellings of the blocks) and\n"
+                 "                        the groups of runs whose overlap with a group's first run is at least arg, in (0, 1]; one summary\n"
+                 "                        line on stderr, the matrix and the groups under \"agreement\" in --metrics_json (R * Q <= 256)\n";
+}
+
+// --agreement T after the runs of a replica batch: the HARD agreement of all R replicas (sbmbp_batch_agreement), the groups at
+// threshold T (sbmbp_agreement_groups), one summary line on stderr; *json = the "agreement" member of --metrics_json, with its
+// leading comma. Nothing goes to stdout.
+int agreement_report(sbmbp_batch_t *bat, uint32_t R, uint32_t best, double threshold, std::string *json) {
+    std::vector<double> ov(size_t(R) * R);
+    std::vector<uint32_t> group(R);
+    uint32_t n_groups = 0;
+    int rc = sbmbp_batch_agreement(bat, SBMBP_AGREE_HARD, nullptr, R, nullptr, ov.data(), nullptr);
+    if (rc == SBMBP_OK) rc = sbmbp_agreement_groups(R, ov.data(), threshold, group.data(), &n_groups);
+    if (rc != SBMBP_OK) return rc;
+    std::vector<uint32_t> size(n_groups, 0u);
+    for (uint32_t r = 0; r < R; ++r) ++size[group[r]];
+    std::clog << "agreement: " << n_groups << (n_groups == 1 ? " group" : " groups") << " at threshold " << threshold << ", sizes";
+    for (uint32_t k = 0; k < n_groups; ++k) std::clog << " " << size[k];
+    std::clog << "; best run " << best << " is in group " << group[best] << " (" << size[group[best]] << " of " << R << " runs)\n";
+    std::ostringstream o;
+    o << std::setprecision(15) << ",\"agreement\":{\"kind\":\"hard\",\"threshold\":" << threshold << std::setprecision(17) << ",\"overlap\":[";
+    for (uint32_t x = 0; x < R; ++x) {
+        o << (x ? "," : "") << "[";
+        for (uint32_t y = 0; y < R; ++y) o << (y ? "," : "") << ov[size_t(x) * R + y];
+        o << "]";
+    }
+    o << "],\"group\":[";
+    for (uint32_t r = 0; r < R; ++r) o << (r ? "," : "") << group[r];
+    o << "],\"n_groups\":" << n_groups << "}";
+    *json = o.str();
+    return SBMBP_OK;
 }
 
 bool read_column(const std::string &path, std::vector<long long> &out) {  // load_beliefs/load_confs (graph_utilities.cpp:8-40)
@@ -372,6 +406,17 @@ int main(int argc, char const *argv[]) {
         else if (Q > 16) conflict = "--learn_restarts cannot be combined with more than 16 blocks (Q > 16)";
         if (conflict) { std::clog << "bp: " << conflict << "\n"; return 1; }
     }
+    // agreement of the restarts (sbmbp_batch_agreement) after the runs
+    const bool have_agreement = var_map.count("agreement") > 0;
+    const double agree_t = have_agreement ? num("agreement", 0.0) : 0.0;
+    if (have_agreement) {
+        const char *conflict = nullptr;
+        const long long runs = std::max(restarts, lrestarts);
+        if (runs <= 1) conflict = "--agreement needs --restarts or --learn_restarts above 1 (it compares the runs of a replica batch)";
+        else if (!(agree_t > 0.0 && agree_t <= 1.0)) conflict = "--agreement needs a threshold in (0, 1]";
+        else if (runs * (long long)Q > 256) conflict = "--agreement cannot compare more than 256 / Q runs at once (restarts * Q above 256)";
+        if (conflict) { std::clog << "bp: " << conflict << "\n"; return 1; }
+    }
     // per-vertex priors (sbmbp_set_vertex_prior): what they cannot be combined with, then the file, both before any device work
     std::vector<double> prior;
     uint64_t prior_rows = 0;
@@ -422,6 +467,8 @@ int main(int argc, char const *argv[]) {
             }
         }
         stage("inference (all replicas)");
+        std::string agree_json;
+        if (have_agreement && (rc = agreement_report(bat, R, best, agree_t, &agree_json)) != SBMBP_OK) return fail(rc);
         if (var_map.count("metrics_json")) {
             const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             sbmbp_stats st;
@@ -449,7 +496,7 @@ int main(int argc, char const *argv[]) {
                 a_gl.push_back(std::to_string(gl));
             }
             arr("seed", a_seed); arr("niter", a_niter); arr("free_energy", a_f); arr("overlap", a_ov); arr("field_level", a_fl); arr("generic_level", a_gl);
-            mj << "}\n";
+            mj << agree_json << "}\n";
         }
         sbmbp_batch_destroy(bat);
         sbmbp_graph_destroy(graph);
@@ -487,6 +534,8 @@ int main(int argc, char const *argv[]) {
         }
         std::clog << "overlap:" << res[best].overlap << "\n";
         stage("learning (all replicas)");
+        std::string agree_json;
+        if (have_agreement && (rc = agreement_report(bat, R, best, agree_t, &agree_json)) != SBMBP_OK) return fail(rc);
         if (var_map.count("metrics_json")) {
             const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             sbmbp_stats st;
@@ -511,7 +560,7 @@ int main(int argc, char const *argv[]) {
                 a_sw.push_back(std::to_string(res[r].total_sweeps));
             }
             arr("seed", a_seed); arr("em_steps", a_steps); arr("status", a_status); arr("free_energy", a_f); arr("total_sweeps", a_sw);
-            mj << "}\n";
+            mj << agree_json << "}\n";
         }
         sbmbp_batch_destroy(bat);
         sbmbp_graph_destroy(graph);

@@ -2365,6 +2365,13 @@ struct sbmbp_batch {
     double *d_prior_shared = nullptr, *d_prior_ones = nullptr;
     const double **d_prior_tab = nullptr;
     uint32_t n_prior = 0;
+    // agreement of replicas (sbmbp_batch_agreement), all allocated on first need: the slots of the listed replicas, the
+    // partial tables of k_agree (grown like the EM partials), the folded n n Q Q results, and the page-locked host side
+    // (AG_MAXN slots, then the results). Capacities in bytes; not counted in device_bytes: the call leaves every statistic alone
+    uint32_t *d_ag_slot = nullptr;
+    double *d_ag_part = nullptr, *d_ag_res = nullptr;
+    size_t ag_slot_cap = 0, ag_part_cap = 0, ag_res_cap = 0, h_ag_cap = 0;
+    void *h_ag = nullptr;
 };
 
 namespace {
@@ -2585,10 +2592,10 @@ void batch_free(sbmbp_batch *b) {
         b->e->d_P = nullptr;
     }
     void *ptrs[] = {b->d_M, b->d_psi, b->d_rec, b->d_P, b->d_par, b->d_cs, b->d_em_in, b->d_em_part[0], b->d_em_part[1], b->d_em_part[2], b->d_em_res,
-                    b->d_prior_shared, b->d_prior_ones, b->d_prior_tab};
+                    b->d_prior_shared, b->d_prior_ones, b->d_prior_tab, b->d_ag_slot, b->d_ag_part, b->d_ag_res};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (batch_replica &p : b->rep) if (p.d_prior) (void)hipFree(p.d_prior);
-    void *hptrs[] = {b->h_cs, b->h_em_in, b->h_em_res};
+    void *hptrs[] = {b->h_cs, b->h_em_in, b->h_em_res, b->h_ag};
     for (void *p : hptrs) if (p) (void)hipHostFree(p);
     for (auto ev : b->ev_cs) if (ev) (void)hipEventDestroy(ev);
     if (b->e) sbmbp_destroy(b->e);
@@ -2752,6 +2759,95 @@ int batch_reductions(sbmbp_batch *b, const uint8_t *mask, double *na_e, double *
             const double fp[3] = {p4[0], p4[1], ne[0]};
             if (parts) std::copy(fp, fp + 3, parts + 3 * size_t(r));
             if (f) f[r] = free_energy_of(fp);
+        }
+    }
+    return SBMBP_OK;
+}
+
+// ---- agreement of replicas (sbmbp.h: sbmbp_batch_agreement; kernels_batch.h: k_agree, k_agree_fold) ---------------------
+// kind and tiles per wave bound together, in the manner of DISPATCH_QB: the statement sees `constexpr int KK, TT`
+#define DISPATCH_AGREE_T(tpw, ...)                                       \
+    switch (tpw) {                                                       \
+        case 1: { constexpr int TT = 1; __VA_ARGS__; } break;            \
+        case 4: { constexpr int TT = 4; __VA_ARGS__; } break;            \
+        default: { constexpr int TT = 16; __VA_ARGS__; } break;          \
+    }
+#define DISPATCH_AGREE(kind, tpw, ...)                                               \
+    switch (kind) {                                                                  \
+        case 0: { constexpr int KK = 0; DISPATCH_AGREE_T(tpw, __VA_ARGS__) } break;  \
+        case 1: { constexpr int KK = 1; DISPATCH_AGREE_T(tpw, __VA_ARGS__) } break;  \
+        default: { constexpr int KK = 2; DISPATCH_AGREE_T(tpw, __VA_ARGS__) } break; \
+    }
+
+constexpr size_t AG_PART_BUDGET = size_t(8) << 20;  // doubles (64 MiB): the most the partial tables of k_agree may take
+constexpr uint32_t AG_GRID = 1024;                  // workgroups of one k_agree launch, about four per CU
+
+template <int KIND, int TPW>
+int launch_agree(hipStream_t st, dim3 grid, size_t lds, const double *psi, const uint32_t *slot, size_t psi_stride, uint32_t N, uint32_t Q, uint32_t n,
+                 uint32_t tile_rows, double *partials) {
+    // (above 64 KB of dynamic LDS the runtime wants to be told; CP = 256 takes 68.5 KB)
+    if (lds > 65536) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_agree<KIND, TPW>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+    hipLaunchKernelGGL((k_agree<KIND, TPW>), grid, dim3(AG_TPB), lds, st, psi, slot, psi_stride, N, Q, n, tile_rows, partials);
+    return SBMBP_OK;
+}
+
+// The arguments have been checked. Reads the marginal tables of the listed replicas and nothing else; writes only the
+// agreement buffers of the batch. The parities are the host's: every call that moves a replica's parity (batch_run, the
+// state setters) returns after the stream has drained, so rep[r].par is current, while d_par holds the parities at the START
+// of the last run and stays untouched here. The launches go behind whatever the stream holds.
+int batch_agreement(sbmbp_batch *b, int kind, const uint32_t *list, uint32_t n, double *confusion, double *overlap, uint32_t *perm) {
+    sbmbp_engine *e = b->e;
+    const uint32_t R = b->R, Q = e->Q, N = e->N, nQ = n * Q, CT = (nQ + 15) / 16, CP = 16 * CT;
+    // tiles per wave and tile rows per workgroup: 4 TPW accumulator tiles hold tile_rows rows of CT tiles
+    const int tpw = CT * CT <= 4 ? 1 : (CT * CT <= 16 ? 4 : 16);
+    const uint32_t tile_rows = std::min<uint32_t>(CT, uint32_t(4 * tpw) / CT), gy = (CT + tile_rows - 1) / tile_rows;
+    const uint32_t n_trips = std::max<uint32_t>(1, (N + AG_V - 1) / AG_V);
+    // workgroups along the vertices: at least four trips each (the set-up of the tile keys and the final store are paid once),
+    // at most AG_GRID in the launch, and partial tables within the budget (at CP = 256 a table is 512 KB: 128 of them)
+    const uint32_t gx = uint32_t(std::max<size_t>(1, std::min<size_t>({size_t((n_trips + 3) / 4), size_t(AG_GRID / gy), AG_PART_BUDGET / (size_t(CP) * CP)})));
+    const size_t n_res = size_t(nQ) * nQ, h_bytes = size_t(AG_MAXN) * sizeof(uint32_t) + n_res * 8;
+    // grown, never shrunk, like the EM partials - but outside device_bytes: the call changes no statistic of the batch
+    auto ensure = [](void **p, size_t *cap, size_t bytes) -> int {
+        if (bytes <= *cap) return SBMBP_OK;
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+        *cap = 0;
+        const hipError_t r = hipMalloc(p, bytes);
+        if (r != hipSuccess) {
+            set_error(std::string("hipMalloc(") + std::to_string(bytes) + " B): " + hipGetErrorString(r));
+            return r == hipErrorOutOfMemory ? SBMBP_ERR_NOMEM : SBMBP_ERR_HIP;
+        }
+        *cap = bytes;
+        return SBMBP_OK;
+    };
+    CHK(ensure(reinterpret_cast<void **>(&b->d_ag_slot), &b->ag_slot_cap, size_t(AG_MAXN) * sizeof(uint32_t)));
+    CHK(ensure(reinterpret_cast<void **>(&b->d_ag_part), &b->ag_part_cap, size_t(gx) * CP * CP * 8));
+    CHK(ensure(reinterpret_cast<void **>(&b->d_ag_res), &b->ag_res_cap, n_res * 8));
+    if (b->h_ag_cap < h_bytes) {
+        if (b->h_ag) { (void)hipHostFree(b->h_ag); b->h_ag = nullptr; b->h_ag_cap = 0; }
+        HIPCHK(hipHostMalloc(&b->h_ag, h_bytes, hipHostMallocDefault));
+        b->h_ag_cap = h_bytes;
+    }
+    uint32_t *h_slot = static_cast<uint32_t *>(b->h_ag);
+    const double *res = reinterpret_cast<const double *>(h_slot + AG_MAXN);
+    for (uint32_t x = 0; x < n; ++x) {
+        const uint32_t r = list ? list[x] : x;
+        h_slot[x] = uint32_t(b->rep[r].par) * R + r;
+    }
+    hipStream_t st = e->stream;
+    HIPCHK(hipMemcpyAsync(b->d_ag_slot, h_slot, size_t(n) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    DISPATCH_AGREE(kind, tpw, CHK((launch_agree<KK, TT>(st, dim3(gx, gy), agree_lds_bytes(CP, n), b->d_psi, b->d_ag_slot, b->psi_stride, N, Q, n, tile_rows,
+                                                        b->d_ag_part))));
+    hipLaunchKernelGGL(k_agree_fold, dim3(uint32_t((n_res + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, b->d_ag_part, gx, CP, Q, n, b->d_ag_res);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(const_cast<double *>(res), b->d_ag_res, n_res * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (confusion) std::copy(res, res + n_res, confusion);
+    if (overlap || perm) {
+        std::vector<uint32_t> pi(Q);
+        for (size_t xy = 0; xy < size_t(n) * n; ++xy) {
+            const double s = best_assignment(Q, res + xy * Q * Q, pi.data());
+            if (overlap) overlap[xy] = s / double(N);
+            if (perm) std::copy(pi.begin(), pi.end(), perm + xy * Q);
         }
     }
     return SBMBP_OK;
@@ -3185,6 +3281,41 @@ int sbmbp_batch_get_stats(sbmbp_batch_t *b, sbmbp_stats *out) {
     out->n_hub_rows = e->n_hub;
     out->hub_edges = e->hub_edges;
     out->psi_form_sweeps = 0;
+    return SBMBP_OK;
+}
+
+int sbmbp_batch_agreement(sbmbp_batch_t *b, int kind, const uint32_t *replicas, uint32_t n, double *confusion, double *overlap, uint32_t *perm) {
+    if (!b) { set_error("sbmbp_batch_agreement: null batch"); return SBMBP_ERR_ARG; }
+    if (kind < 0 || kind > 2) { set_error("sbmbp_batch_agreement: kind " + std::to_string(kind) + " (0 soft, 1 hard-soft, 2 hard)"); return SBMBP_ERR_ARG; }
+    const uint32_t R = b->R, Q = b->e->Q;
+    if (replicas && n == 0) { set_error("sbmbp_batch_agreement: a replica list needs n >= 1"); return SBMBP_ERR_ARG; }
+    if (!replicas) n = R;
+    std::vector<char> seen(R, 0);
+    for (uint32_t x = 0; x < n; ++x) {
+        const uint32_t r = replicas ? replicas[x] : x;
+        if (r >= R) { set_error("sbmbp_batch_agreement: replica index " + std::to_string(r) + " outside the batch of " + std::to_string(R)); return SBMBP_ERR_ARG; }
+        if (seen[r]) { set_error("sbmbp_batch_agreement: replica " + std::to_string(r) + " is listed twice"); return SBMBP_ERR_ARG; }
+        seen[r] = 1;
+    }
+    if (uint64_t(n) * Q > uint64_t(AG_CPMAX)) {
+        set_error("sbmbp_batch_agreement: " + std::to_string(n) + " replicas of " + std::to_string(Q) + " labels are " + std::to_string(uint64_t(n) * Q) +
+                  " columns, above " + std::to_string(AG_CPMAX) + ": pass a subset list of replicas");
+        return SBMBP_ERR_UNSUPPORTED;
+    }
+    for (uint32_t x = 0; x < n; ++x) {
+        const uint32_t r = replicas ? replicas[x] : x;
+        if (!b->rep[r].have_state) {
+            set_error("sbmbp_batch_agreement: replica " + std::to_string(r) + " has no state (init_messages / set_state first)");
+            return SBMBP_ERR_STATE;
+        }
+    }
+    device_scope dev_(b->e);
+    return batch_agreement(b, kind, replicas, n, confusion, overlap, perm);
+}
+
+int sbmbp_agreement_groups(uint32_t n, const double *overlap, double threshold, uint32_t *group, uint32_t *n_groups) {
+    if ((n && (!overlap || !group)) || !n_groups) return arg_error(__func__, __LINE__);
+    *n_groups = agreement_groups(n, overlap, threshold, group);
     return SBMBP_OK;
 }
 

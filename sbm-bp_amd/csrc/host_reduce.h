@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <limits>
 #include <numeric>
 #include <vector>
 
@@ -173,6 +174,66 @@ inline double best_overlap(uint32_t Q, uint32_t N, const double *C) {
         if (Q > 8) break;
     } while (std::next_permutation(perm.begin(), perm.end()));
     return best;
+}
+
+// Agreement of two runs (sbmbp.h: sbmbp_batch_agreement): the permutation perm of the labels that maximises
+// sum_a C[a * Q + perm[a]] over all Q! of them, exactly, for any Q: the maximum-weight assignment by the Hungarian method
+// with potentials (O(Q^3); rows are inserted one after the other along shortest augmenting paths of the costs -C). A NaN
+// entry counts as 0. Returns the sum of the C entries the assignment picks, added in the order a = 0 .. Q-1. best_overlap
+// above is the reference's rule for the overlap with the TRUE configuration and stays what it is.
+inline double best_assignment(uint32_t Q, const double *C, uint32_t *perm) {
+    const double INF = std::numeric_limits<double>::infinity();
+    auto cost = [&](uint32_t a, uint32_t b) { const double c = C[size_t(a) * Q + b]; return std::isnan(c) ? 0.0 : -c; };
+    // 1-based rows / columns; column 0 is the virtual start. row_of[b] = row matched to column b (0 = none)
+    std::vector<double> u(Q + 1, 0.0), v(Q + 1, 0.0), minv(Q + 1);
+    std::vector<uint32_t> row_of(Q + 1, 0u), way(Q + 1, 0u);
+    std::vector<char> used(Q + 1);
+    for (uint32_t a = 1; a <= Q; ++a) {
+        row_of[0] = a;
+        uint32_t b0 = 0;
+        std::fill(minv.begin(), minv.end(), INF);
+        std::fill(used.begin(), used.end(), char(0));
+        do {
+            used[b0] = 1;
+            const uint32_t a0 = row_of[b0];
+            double delta = INF;
+            uint32_t b1 = 0;
+            for (uint32_t b = 1; b <= Q; ++b) {
+                if (used[b]) continue;
+                const double cur = cost(a0 - 1, b - 1) - u[a0] - v[b];
+                if (cur < minv[b]) { minv[b] = cur; way[b] = b0; }
+                if (b1 == 0 || minv[b] < delta) { delta = minv[b]; b1 = b; }  // b1 != 0 after the first free column: an Inf entry cannot strand the search
+            }
+            for (uint32_t b = 0; b <= Q; ++b) {
+                if (used[b]) { u[row_of[b]] += delta; v[b] -= delta; }
+                else minv[b] -= delta;
+            }
+            b0 = b1;
+        } while (row_of[b0] != 0);
+        do {  // augment along the path found
+            const uint32_t b1 = way[b0];
+            row_of[b0] = row_of[b1];
+            b0 = b1;
+        } while (b0 != 0);
+    }
+    for (uint32_t b = 1; b <= Q; ++b) perm[row_of[b] - 1] = b - 1;
+    double s = 0.0;
+    for (uint32_t a = 0; a < Q; ++a) s += C[size_t(a) * Q + perm[a]];
+    return s;
+}
+
+// Groups of runs from their n x n overlap matrix (sbmbp.h: sbmbp_agreement_groups): runs in ascending order; x joins the
+// group of the FIRST earlier leader g with overlap[g * n + x] >= threshold, else it leads a new group. Returns the number
+// of groups; group[x] = the group's number in order of creation. A NaN overlap never passes.
+inline uint32_t agreement_groups(uint32_t n, const double *overlap, double threshold, uint32_t *group) {
+    std::vector<uint32_t> leader;
+    for (uint32_t x = 0; x < n; ++x) {
+        uint32_t k = 0;
+        while (k < leader.size() && !(overlap[size_t(leader[k]) * n + x] >= threshold)) ++k;
+        if (k == leader.size()) leader.push_back(x);
+        group[x] = k;
+    }
+    return uint32_t(leader.size());
 }
 
 // which of n runs is best (sbmbp.h: sbmbp_best_replica): the lowest free energy that is not NaN among the runs of the

@@ -21,6 +21,7 @@
 #define SBMBP_KERNELS_BATCH_H
 
 #include "kernels.h"
+#include "kernels_wide.h"  // d4: the accumulator of v_mfma_f64_16x16x4_f64 (k_agree)
 
 namespace sbmbp {
 
@@ -400,6 +401,153 @@ k_fold_batch(const double *__restrict__ in, const int *__restrict__ active, uint
     for (uint32_t r = threadIdx.x & 63; r < rows; r += 64) a += p[size_t(r) * cols];
     a = wave_sum(a);
     if ((threadIdx.x & 63) == 0) out[size_t(rep) * out_stride + out_off + c] = a;
+}
+
+// ================================================================================================
+// Agreement of replicas (sbmbp_batch_agreement): the Gram matrix G = X^T Y over the marginal tables of the n listed
+// replicas. Rows = vertices, column c = x Q + q (listed replica x, label q), padded with zeros to CP = 16 ceil(n Q / 16) <= 256.
+//   kind 0 (soft)       X = Y = Psi          kind 2 (hard)   X = Y = H, the one-hot image of l_i = argmax_q psi_i[q]
+//   kind 1 (hard-soft)  X = H, Y = Psi       C_xy = the Q x Q block of G at (x Q, y Q)
+// It is k_wem's shape of work (kernels_wide.h) with the vertices as the long axis, and k_wem's operand mapping of
+// v_mfma_f64_16x16x4_f64: A: lane l holds X[vertex 4 step + (l >> 4)][16 at + (l & 15)], B: Y likewise with bt, C/D: lane l,
+// register r = row (l >> 4) + 4 r, column l & 15.
+// A workgroup walks trips of AG_V vertices (trip blockIdx.x, + gridDim.x, ...). Staging: the AG_V rows of listed replica x
+// are AG_V Q consecutive doubles at (slot[x] psi_stride + v0 Q), slot[x] = parity R + replica; the flat index over (x, row,
+// label) goes over the threads, so a wave reads consecutive addresses, with the streaming loads of the reductions, eight in
+// flight per thread before the first is stored. The image is [vertex][column] with a row stride of S = CP or CP + 16 doubles,
+// whichever is 16 mod 32: lanes l and l + 16 of an operand read (ds_read_b64: 64 banks of 4 bytes, conflicts inside a
+// 32-lane half) then sit on opposite halves of the bank row. Columns >= n Q and vertices >= N are written as zeros on EVERY
+// trip. The hard kinds keep no one-hot image: a byte per (vertex, replica) holds l_i (254 for a vertex >= N), and an operand
+// is (label == the lane's q) ? 1 : 0 with the lane's (x, q) of every tile packed in a register before the first trip (a
+// column >= n Q asks for label 255, which no row has). Ties go to the lowest label, a NaN never wins, a row of NaNs gives 0.
+// Every wave owns the tiles wave + 4 u, u < TPW, of its workgroup's tile rows [blockIdx.y tile_rows, + tile_rows) in
+// accumulators; the host picks TPW in {1, 4, 16} and tile_rows so that 4 TPW >= tile_rows CP / 16: one pass up to CP = 128,
+// 2 .. 4 workgroup rows above, each of which stages the whole table again (from L2 / Infinity Cache).
+// A workgroup writes its sums once: partials[blockIdx.x][CP][CP]; k_agree_fold adds them in index order. No atomics: two
+// calls give the same bits. In kind 2 every term is 0 or 1, so the sums are exact whatever the order.
+// ================================================================================================
+constexpr int AG_V = 32, AG_TPB = 256, AG_MAXN = 128, AG_CPMAX = 256;
+static_assert(AG_V % 4 == 0 && (AG_V & (AG_V - 1)) == 0, "a trip is whole MFMA steps; the staging shifts by log2(AG_V)");
+__host__ __device__ constexpr uint32_t agree_row_stride(uint32_t CP) { return (CP & 16u) ? CP : CP + 16u; }
+// dynamic LDS of k_agree: the image and the label bytes
+__host__ __device__ constexpr size_t agree_lds_bytes(uint32_t CP, uint32_t n) { return size_t(AG_V) * agree_row_stride(CP) * 8 + size_t(AG_V) * ((n + 7u) & ~7u); }
+
+template <int KIND, int TPW>
+__global__ void __launch_bounds__(AG_TPB)
+k_agree(const double *__restrict__ psi_all, const uint32_t *__restrict__ slot /* [n] */, size_t psi_stride, uint32_t N, uint32_t Q, uint32_t n,
+        uint32_t tile_rows, double *__restrict__ partials) {
+    extern __shared__ double ag_img[];  // [AG_V][S], then the labels [AG_V][LN]
+    __shared__ uint32_t s_slot[AG_MAXN];
+    constexpr bool HARD_A = KIND != 0, HARD_B = KIND == 2;
+    const uint32_t nQ = n * Q, CT = (nQ + 15u) / 16u, CP = 16u * CT, S = agree_row_stride(CP), LN = (n + 7u) & ~7u;
+    uint8_t *s_lab = reinterpret_cast<uint8_t *>(ag_img + size_t(AG_V) * S);
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u, le = lane & 15u, g = lane >> 4;
+    const uint32_t magic = ((1u << 20) + Q - 1u) / Q;  // m / Q == (m * magic) >> 20 for m < 65536, Q <= 16
+    const uint32_t tr0 = blockIdx.y * tile_rows;
+    const uint32_t n_tiles = min(tile_rows, CT - tr0) * CT;  // of this workgroup; the host keeps tr0 < CT
+
+    // what the lane fetches for tile u: the image column, or (x << 8 | q) of its column for a hard operand
+    auto key_of = [&](uint32_t col, bool hard) -> uint32_t {
+        if (!hard) return col;
+        if (col >= nQ) return 255u;
+        const uint32_t x = (col * magic) >> 20;
+        return (x << 8) | (col - x * Q);
+    };
+    uint32_t ka[TPW], kb[TPW];
+    d4 acc[TPW];
+#pragma unroll
+    for (int u = 0; u < TPW; ++u) {
+        const uint32_t t = min(wave + 4u * uint32_t(u), n_tiles - 1u), tr = t / CT;
+        ka[u] = key_of(16u * (tr0 + tr) + le, HARD_A);
+        kb[u] = key_of(16u * (t - tr * CT) + le, HARD_B);
+        acc[u] = d4{0.0, 0.0, 0.0, 0.0};
+    }
+    for (uint32_t x = tid; x < n; x += AG_TPB) s_slot[x] = slot[x];
+
+    const uint32_t total = uint32_t(AG_V) * nQ;  // doubles of a trip, flat over (x, row, label)
+    const uint32_t n_trips = (N + AG_V - 1u) / AG_V;
+    for (uint32_t trip = blockIdx.x; trip < n_trips; trip += gridDim.x) {
+        const uint32_t v0 = trip * AG_V;
+        __syncthreads();  // the trip before has been consumed (and s_slot is there)
+        for (uint32_t f0 = tid; f0 < total; f0 += 8u * AG_TPB) {
+            double val[8];
+            uint32_t dst[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const uint32_t f = f0 + uint32_t(k) * AG_TPB;
+                val[k] = 0.0;
+                dst[k] = ~0u;
+                if (f < total) {
+                    const uint32_t row = (f * magic) >> 20, x = row / AG_V, v = row % AG_V, q = f - row * Q;  // row = x AG_V + v
+                    dst[k] = v * S + x * Q + q;
+                    if (v0 + v < N) val[k] = __builtin_nontemporal_load(psi_all + size_t(s_slot[x]) * psi_stride + size_t(v0) * Q + (f - x * AG_V * Q));
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (dst[k] != ~0u) ag_img[dst[k]] = val[k];
+        }
+        if (!HARD_B)  // the image is an operand: its padding columns are zeros on every trip
+            for (uint32_t z = tid; z < uint32_t(AG_V) * 16u; z += AG_TPB) {
+                const uint32_t c = nQ + (z & 15u);
+                if (c < CP) ag_img[(z >> 4) * S + c] = 0.0;
+            }
+        if (HARD_A) {
+            __syncthreads();
+            for (uint32_t p = tid; p < uint32_t(AG_V) * n; p += AG_TPB) {
+                const uint32_t x = p / AG_V, v = p % AG_V;
+                const double *row = ag_img + v * S + x * Q;
+                uint32_t idx = 0;
+                double best = row[0];
+                if (best != best) best = -INFINITY;
+                for (uint32_t q = 1; q < Q; ++q) {
+                    const double w = row[q];
+                    if (w > best) { best = w; idx = q; }
+                }
+                s_lab[v * LN + x] = uint8_t(v0 + v < N ? idx : 254u);
+            }
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (uint32_t step = 0; step < uint32_t(AG_V) / 4u; ++step) {
+            const double *irow = ag_img + (4u * step + g) * S;
+            const uint8_t *lrow = s_lab + (4u * step + g) * LN;
+#pragma unroll
+            for (int u = 0; u < TPW; ++u) {
+                if (wave + 4u * uint32_t(u) < n_tiles) {  // wave-uniform
+                    const double a = HARD_A ? (uint32_t(lrow[ka[u] >> 8]) == (ka[u] & 255u) ? 1.0 : 0.0) : irow[ka[u]];
+                    const double b = HARD_B ? (uint32_t(lrow[kb[u] >> 8]) == (kb[u] & 255u) ? 1.0 : 0.0) : irow[kb[u]];
+                    acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[u], 0, 0, 0);
+                }
+            }
+        }
+    }
+    // C/D layout: lane l, register r: row (l >> 4) + 4 r of the tile, column l & 15
+    double *__restrict__ out = partials + size_t(blockIdx.x) * CP * CP;
+#pragma unroll
+    for (int u = 0; u < TPW; ++u) {
+        const uint32_t t = wave + 4u * uint32_t(u);
+        if (t < n_tiles) {
+            const uint32_t tr = t / CT, at = tr0 + tr, bt = t - tr * CT;
+            const double v[4] = {acc[u].x, acc[u].y, acc[u].z, acc[u].w};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) out[size_t(16u * at + g + 4u * uint32_t(r)) * CP + 16u * bt + le] = v[r];
+        }
+    }
+}
+
+// fold of the n_part partial tables in index order, one thread per entry of the n Q x n Q result, written in the layout
+// of the interface: out[((x n + y) Q + a) Q + b]
+__global__ void __launch_bounds__(BLOCK)
+k_agree_fold(const double *__restrict__ partials, uint32_t n_part, uint32_t CP, uint32_t Q, uint32_t n, double *__restrict__ out) {
+    const uint32_t nQ = n * Q, idx = blockIdx.x * BLOCK + threadIdx.x;
+    if (idx >= nQ * nQ) return;
+    const uint32_t i = idx / nQ, j = idx - i * nQ;
+    const double *__restrict__ p = partials + size_t(i) * CP + j;
+    double s = 0.0;
+    for (uint32_t k = 0; k < n_part; ++k) s += p[size_t(k) * CP * CP];
+    const uint32_t x = i / Q, a = i - x * Q, y = j / Q, b = j - y * Q;
+    out[((size_t(x) * n + y) * Q + a) * Q + b] = s;
 }
 
 }  // namespace sbmbp
