@@ -43,7 +43,7 @@ def _hipcc():
 
 def build_lib(force=False, verbose=False):
     srcs = [os.path.join(CSRC, f) for f in ("engine.hip", "dist.hip", "host_graph.cpp")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("kernels.h", "kernels_wide.h", "kernels_batch.h", "sweep_msg_body.inc", "sweep_step_body.inc", "fe_frame_body.inc", "fe_hub_body.inc", "em_frame_body.inc", "host_graph.h", "host_loops.h", "host_reduce.h")] + [os.path.join(ROOT, "include", "sbmbp.h")]
+    deps = srcs + [os.path.join(CSRC, f) for f in ("kernels.h", "kernels_wide.h", "kernels_batch.h", "sweep_msg_body.inc", "sweep_step_body.inc", "fe_frame_body.inc", "fe_hub_body.inc", "em_frame_body.inc", "device_buffer.h", "host_graph.h", "host_loops.h", "host_reduce.h")] + [os.path.join(ROOT, "include", "sbmbp.h")]
     out = os.path.join(CSRC, "libsbmbp_hip.so")
     if force or _newer(out, deps):
         cmd = [_hipcc(), "-std=c++14", "-O3", "--offload-arch=" + ARCH, "-fPIC", "-shared", "-pthread", "-o", out] + srcs + ["-lrccl"]

@@ -23,12 +23,15 @@
 #include <vector>
 
 #include "../../include/sbmbp.h"
+#include "device_buffer.h"
 #include "host_graph.h"
 #include "host_loops.h"
 #include "host_reduce.h"
 
 using sbmbp::set_error;
 using sbmbp::arg_error;
+using sbmbp::device_buffer;
+using sbmbp::pinned_buffer;
 typedef uint32_t u32;
 typedef uint64_t u64;
 
@@ -351,22 +354,14 @@ struct sbmbp_comm {
     std::atomic<bool> aborted{false};  // sbmbp_comm_abort may come from ANOTHER thread (a rank that failed outside a collective)
     std::shared_ptr<local_group> grp;
     sbmbp_comm_callbacks cb{};
-    double *h_a = nullptr, *h_b = nullptr;  // page-locked staging (callbacks)
-    size_t h_cap = 0;
+    pinned_buffer<double> h_a, h_b;  // staging (callbacks), grown together
 };
 
 namespace {
 
 int ensure_host(sbmbp_comm *c, size_t doubles) {
-    if (doubles <= c->h_cap) return SBMBP_OK;
-    if (c->h_a) (void)hipHostFree(c->h_a);
-    if (c->h_b) (void)hipHostFree(c->h_b);
-    c->h_a = c->h_b = nullptr;
-    c->h_cap = 0;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_a), doubles * 8, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_b), doubles * 8, hipHostMallocDefault));
-    c->h_cap = doubles;
-    return SBMBP_OK;
+    CHK(c->h_a.ensure(doubles));
+    return c->h_b.ensure(doubles);
 }
 
 u64 sum_counts(const u64 *c, int n) { u64 s = 0; for (int i = 0; i < n; ++i) s += c[i]; return s; }
@@ -601,8 +596,6 @@ void sbmbp_comm_destroy(sbmbp_comm_t *c) {
         if (me.done) (void)hipEventDestroy(me.done);
         me.ready = me.done = nullptr;
     }
-    if (c->h_a) (void)hipHostFree(c->h_a);
-    if (c->h_b) (void)hipHostFree(c->h_b);
     delete c;
 }
 
@@ -628,22 +621,39 @@ const char *sbmbp_comm_transport(const sbmbp_comm_t *c) { return !c ? "" : (c->k
 // =====================================================================================================
 // The per-rank driver
 // =====================================================================================================
-struct sbmbp_dist {
-    sbmbp_comm *comm = nullptr;
-    const sbmbp_graph_t *graph = nullptr;  // borrowed: must outlive the engine, as the adjacency must in the reference (belief_propagation.h:27)
-    int rank = 0, world = 1, device = 0;
-    u32 Q = 0, dc = 0, ncomp = 0;
-    shard_plan plan;
-    sbmbp_engine_t *eng = nullptr;
+// The rank's streams and events, as a base of the driver: the buffers are members of sbmbp_dist, so they are released after
+// ~sbmbp_dist has drained the streams and destroyed the shard engine, and before this destructor destroys the streams.
+struct dist_streams {
+    int device = 0;
     hipStream_t s_compute = nullptr, s_comm = nullptr;
     hipStream_t s_aux[2] = {nullptr, nullptr};  // the row chunks of a sweep alternate between two streams: a chunk's tail overlaps the next chunk
     hipEvent_t ev_start = nullptr;
-    bool two_streams = true;
     std::vector<hipEvent_t> ev_chunk, ev_xchg;
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    double *d_psi[2] = {nullptr, nullptr};
-    double *d_red = nullptr, *d_sendbuf = nullptr, *d_recvbuf[2] = {nullptr, nullptr}, *d_msg_send = nullptr, *d_psi_all = nullptr;
-    u32 *d_send_idx = nullptr, *d_stage_to_halo = nullptr, *d_msg_send_edge = nullptr;
+    std::vector<hipEvent_t> phase_ev;  // 4 per timed sweep
+    ~dist_streams() {
+        for (auto ev : ev_chunk) if (ev) (void)hipEventDestroy(ev);
+        for (auto ev : ev_xchg) if (ev) (void)hipEventDestroy(ev);
+        for (auto ev : phase_ev) if (ev) (void)hipEventDestroy(ev);
+        if (ev_a) (void)hipEventDestroy(ev_a);
+        if (ev_b) (void)hipEventDestroy(ev_b);
+        if (ev_start) (void)hipEventDestroy(ev_start);
+        for (auto sx : s_aux) if (sx) (void)hipStreamDestroy(sx);
+        if (s_comm) (void)hipStreamDestroy(s_comm);
+        if (s_compute) (void)hipStreamDestroy(s_compute);
+    }
+};
+struct sbmbp_dist : dist_streams {
+    sbmbp_comm *comm = nullptr;
+    const sbmbp_graph_t *graph = nullptr;  // borrowed: must outlive the engine, as the adjacency must in the reference (belief_propagation.h:27)
+    int rank = 0, world = 1;
+    u32 Q = 0, dc = 0, ncomp = 0;
+    shard_plan plan;
+    sbmbp_engine_t *eng = nullptr;  // borrows d_psi[0], d_psi[1] and d_red (sbmbp_shard_desc), and reads the exchange buffers (sbmbp_shard_set_io)
+    bool two_streams = true;
+    device_buffer<double> d_psi[2];
+    device_buffer<double> d_red, d_sendbuf, d_recvbuf[2], d_msg_send, d_psi_all;
+    device_buffer<u32> d_send_idx, d_stage_to_halo, d_msg_send_edge;
     std::vector<double> cab;
     std::vector<u32> na;
     std::vector<u32> true_conf_own;
@@ -654,10 +664,16 @@ struct sbmbp_dist {
     bool consistent = false;  // psi == marginals of the message pair: the marginal-gather sweep may start at once
     u64 total_sweeps = 0, psi_sweeps = 0;
     bool timing = false;
-    std::vector<hipEvent_t> phase_ev;  // 4 per timed sweep
     size_t phase_used = 0;
     double phase_ms[3] = {0, 0, 0};
     u64 phase_n = 0;
+    ~sbmbp_dist() {
+        (void)hipSetDevice(device);
+        if (s_comm) (void)hipStreamSynchronize(s_comm);
+        for (auto sx : s_aux) if (sx) (void)hipStreamSynchronize(sx);
+        if (s_compute) (void)hipStreamSynchronize(s_compute);
+        if (eng) { (void)sbmbp_set_stream(eng, nullptr); sbmbp_destroy(eng); }
+    }
 };
 
 namespace {
@@ -665,12 +681,6 @@ namespace {
 struct device_guard {  // the current device is a per-thread setting: every entry point selects the rank's GPU
     explicit device_guard(int dev) { (void)hipSetDevice(dev); }
 };
-
-template <typename T> int dalloc(T **p, size_t count) {
-    hipError_t r = hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(count, 1) * sizeof(T));
-    if (r != hipSuccess) { set_error(std::string("hipMalloc: ") + hipGetErrorString(r)); return r == hipErrorOutOfMemory ? SBMBP_ERR_NOMEM : SBMBP_ERR_HIP; }
-    return SBMBP_OK;
-}
 
 inline const u64 *cp_row(const std::vector<u64> &v, u32 c, int W) { return v.data() + size_t(c) * W; }
 
@@ -911,7 +921,7 @@ int fe_terms(sbmbp_dist *d, bool want_entropy, double out[6]) {
     if (d->dc == 0 && sbmbp::nonedge_is_exact(0, N)) {
         // small graphs: the reference's O(N^2) loop exactly, as the single engine does: every rank gets the marginals of all
         // vertices (own rows summed into a global table) and sums its own rows against them
-        if (!d->d_psi_all) CHK(dalloc(&d->d_psi_all, size_t(N) * d->Q));
+        if (!d->d_psi_all) CHK(d->d_psi_all.alloc(size_t(N) * d->Q));
         HIPCHK(hipMemsetAsync(d->d_psi_all, 0, size_t(N) * d->Q * 8, d->s_compute));
         HIPCHK(hipMemcpyAsync(d->d_psi_all + size_t(d->plan.row0) * d->Q, d->d_psi[sbmbp_shard_read_buffer(d->eng, 0)],
                               size_t(d->plan.n_own) * d->Q * 8, hipMemcpyDeviceToDevice, d->s_compute));
@@ -980,8 +990,7 @@ int sbmbp_dist_create(sbmbp_dist_t **out, sbmbp_comm_t *comm, const sbmbp_graph_
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device visible; the engine has no CPU fallback"); return SBMBP_ERR_NODEVICE; }
     if (device >= 0) HIPCHK(hipSetDevice(device));
-    // (a failure half way frees what exists so far: sbmbp_dist_destroy copes with a partly built object)
-    std::unique_ptr<sbmbp_dist, void (*)(sbmbp_dist *)> d(new sbmbp_dist(), sbmbp_dist_destroy);
+    std::unique_ptr<sbmbp_dist> d(new sbmbp_dist());  // (a failure half way releases what exists so far)
     HIPCHK(hipGetDevice(&d->device));
     d->comm = comm;
     d->graph = g;
@@ -997,19 +1006,19 @@ int sbmbp_dist_create(sbmbp_dist_t **out, sbmbp_comm_t *comm, const sbmbp_graph_
     d->ncomp = (env_h && std::string(env_h) == "0") ? Q : Q - 1;
     const size_t n_tab = size_t(P.n_own) + P.n_halo;
     for (int t = 0; t < 2; ++t) {
-        CHK(dalloc(&d->d_psi[t], n_tab * Q));
+        CHK(d->d_psi[t].alloc(n_tab * Q));
         HIPCHK(hipMemset(d->d_psi[t], 0, std::max<size_t>(1, n_tab * Q) * 8));
-        CHK(dalloc(&d->d_recvbuf[t], size_t(P.n_halo) * d->ncomp));
+        CHK(d->d_recvbuf[t].alloc(size_t(P.n_halo) * d->ncomp));
         HIPCHK(hipMemset(d->d_recvbuf[t], 0, std::max<size_t>(1, size_t(P.n_halo) * d->ncomp) * 8));
     }
     const size_t red_cap = std::max<size_t>(8192, SBMBP_RED_GATHER_OFFSET + size_t(d->world) * SBMBP_FOLD_ROWS * (16 + 1));
-    CHK(dalloc(&d->d_red, red_cap));
+    CHK(d->d_red.alloc(red_cap));
     HIPCHK(hipMemset(d->d_red, 0, red_cap * 8));
-    CHK(dalloc(&d->d_sendbuf, P.send_idx_chunked.size() * d->ncomp));
-    CHK(dalloc(&d->d_send_idx, P.send_idx_chunked.size()));
-    CHK(dalloc(&d->d_stage_to_halo, P.n_halo));
-    CHK(dalloc(&d->d_msg_send, size_t(P.n_halo_msgs) * (Q - 1)));
-    CHK(dalloc(&d->d_msg_send_edge, P.n_halo_msgs));
+    CHK(d->d_sendbuf.alloc(P.send_idx_chunked.size() * d->ncomp));
+    CHK(d->d_send_idx.alloc(P.send_idx_chunked.size()));
+    CHK(d->d_stage_to_halo.alloc(P.n_halo));
+    CHK(d->d_msg_send.alloc(size_t(P.n_halo_msgs) * (Q - 1)));
+    CHK(d->d_msg_send_edge.alloc(P.n_halo_msgs));
     if (!P.send_idx_chunked.empty()) HIPCHK(hipMemcpy(d->d_send_idx, P.send_idx_chunked.data(), P.send_idx_chunked.size() * 4, hipMemcpyHostToDevice));
     if (P.n_halo) {
         std::vector<u32> ident(P.n_halo);
@@ -1083,27 +1092,9 @@ int sbmbp_dist_create(sbmbp_dist_t **out, sbmbp_comm_t *comm, const sbmbp_graph_
     return SBMBP_OK;
 }
 
-void sbmbp_dist_destroy(sbmbp_dist_t *d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    if (d->s_comm) (void)hipStreamSynchronize(d->s_comm);
-    for (auto sx : d->s_aux) if (sx) (void)hipStreamSynchronize(sx);
-    if (d->s_compute) (void)hipStreamSynchronize(d->s_compute);
-    if (d->eng) { (void)sbmbp_set_stream(d->eng, nullptr); sbmbp_destroy(d->eng); }
-    void *ptrs[] = {d->d_psi[0], d->d_psi[1], d->d_red, d->d_sendbuf, d->d_recvbuf[0], d->d_recvbuf[1], d->d_msg_send, d->d_psi_all,
-                    d->d_send_idx, d->d_stage_to_halo, d->d_msg_send_edge};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    for (auto ev : d->ev_chunk) if (ev) (void)hipEventDestroy(ev);
-    for (auto ev : d->ev_xchg) if (ev) (void)hipEventDestroy(ev);
-    for (auto ev : d->phase_ev) if (ev) (void)hipEventDestroy(ev);
-    if (d->ev_a) (void)hipEventDestroy(d->ev_a);
-    if (d->ev_b) (void)hipEventDestroy(d->ev_b);
-    if (d->ev_start) (void)hipEventDestroy(d->ev_start);
-    for (auto sx : d->s_aux) if (sx) (void)hipStreamDestroy(sx);
-    if (d->s_comm) (void)hipStreamDestroy(d->s_comm);
-    if (d->s_compute) (void)hipStreamDestroy(d->s_compute);
-    delete d;
-}
+// ~sbmbp_dist drains the streams and destroys the shard engine, the buffers go with the members, ~dist_streams destroys the
+// events and the streams
+void sbmbp_dist_destroy(sbmbp_dist_t *d) { delete d; }
 
 int sbmbp_dist_info(const sbmbp_dist_t *d, sbmbp_dist_info_t *out) {
     if (!d || !out) return arg_error(__func__, __LINE__);
@@ -1200,20 +1191,15 @@ int sbmbp_dist_gather_marginals(sbmbp_dist_t *d, double *psi_all) {
     if (!d || !psi_all) return arg_error(__func__, __LINE__);
     device_guard guard(d->device);
     const u32 N = d->plan.n_global, Q = d->Q;
-    double *tab = nullptr;
-    CHK(dalloc(&tab, size_t(N) * Q));
-    hipError_t err = hipMemsetAsync(tab, 0, size_t(N) * Q * 8, d->s_compute);
-    if (err == hipSuccess)
-        err = hipMemcpyAsync(tab + size_t(d->plan.row0) * Q, d->d_psi[sbmbp_shard_read_buffer(d->eng, 0)], size_t(d->plan.n_own) * Q * 8,
-                             hipMemcpyDeviceToDevice, d->s_compute);
-    int rc = err == hipSuccess ? comm_allreduce(d->comm, tab, size_t(N) * Q, 0, d->s_compute) : SBMBP_ERR_HIP;
-    if (rc == SBMBP_OK) {
-        err = hipMemcpyAsync(psi_all, tab, size_t(N) * Q * 8, hipMemcpyDeviceToHost, d->s_compute);
-        if (err == hipSuccess) err = hipStreamSynchronize(d->s_compute);
-        if (err != hipSuccess) rc = SBMBP_ERR_HIP;
-    }
-    (void)hipFree(tab);
-    return rc;
+    device_buffer<double> tab;
+    CHK(tab.alloc(size_t(N) * Q));
+    HIPCHK(hipMemsetAsync(tab, 0, size_t(N) * Q * 8, d->s_compute));
+    HIPCHK(hipMemcpyAsync(tab + size_t(d->plan.row0) * Q, d->d_psi[sbmbp_shard_read_buffer(d->eng, 0)], size_t(d->plan.n_own) * Q * 8,
+                          hipMemcpyDeviceToDevice, d->s_compute));
+    CHK(comm_allreduce(d->comm, tab, size_t(N) * Q, 0, d->s_compute));
+    HIPCHK(hipMemcpyAsync(psi_all, tab, size_t(N) * Q * 8, hipMemcpyDeviceToHost, d->s_compute));
+    HIPCHK(hipStreamSynchronize(d->s_compute));
+    return SBMBP_OK;
 }
 
 int sbmbp_dist_set_params(sbmbp_dist_t *d, const double *cab, const uint32_t *na, double beta) {

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/sbmbp.h"
+#include "device_buffer.h"
 #include "host_graph.h"
 #include "host_loops.h"
 #include "host_reduce.h"
@@ -39,56 +40,71 @@ using namespace sbmbp;
         if (_r != SBMBP_OK) return _r; \
     } while (0)
 
-struct sbmbp_engine {
+struct conv_state { double maxdiff; int conv_iter, sweep_idx, stop, have_prev, hinted, exact, last_exact, pause, ar_fl, ar_gl; };
+static_assert(offsetof(dev_params, ar_gl) - offsetof(dev_params, maxdiff) == offsetof(conv_state, ar_gl), "conv_state mirrors dev_params from maxdiff on");
+
+// The engine's stream and events, as a base of the engine: the buffers are members of sbmbp_engine, so they are released after
+// ~sbmbp_engine has drained the stream and before this destructor destroys it.
+struct engine_stream {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
+    hipEvent_t ev_cs[2] = {nullptr, nullptr};
+    std::vector<hipEvent_t> ev;  // the pool of the sweep timing
+    ~engine_stream() {
+        for (auto x : ev) (void)hipEventDestroy(x);
+        for (auto x : ev_cs) if (x) (void)hipEventDestroy(x);
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+struct sbmbp_engine : engine_stream {
     uint32_t N = 0, Q = 0, dc = 0;  // N = rows this engine updates (all vertices, or the owned range of a shard)
     bool wide = false;              // Q > 16: the matrix-core kernels of kernels_wide.h (full Q-component message records)
-    dev_wide *d_Pw = nullptr;
+    device_buffer<dev_wide> d_Pw;
     uint64_t E2 = 0;
     // sharding (sbmbp_shard_create): marginal table = owned rows followed by halo vertices
-    bool sharded = false, ext_psi = false;
+    bool sharded = false;
     uint32_t Nglob = 0, n_halo = 0, row0 = 0;
     uint64_t edge0 = 0;
-    double *d_red = nullptr;  // caller-owned reduction hand-off buffer (shards)
-    double *d_Min = nullptr;  // shards: materialised incoming messages for the reductions (allocated on first use)
-    uint32_t *d_snd_ptr = nullptr, *d_snd_slot = nullptr;  // shards: fused exchange buffers (sbmbp_shard_set_io)
+    device_buffer<double> d_red;  // shards: the reduction hand-off buffer, borrowed from the caller (sbmbp_shard_desc::red_buf)
+    device_buffer<double> d_Min;  // shards: materialised incoming messages for the reductions (allocated on first use)
+    device_buffer<uint32_t> d_snd_ptr, d_snd_slot;  // shards: fused exchange buffers (sbmbp_shard_set_io)
     double *io_sendbuf = nullptr;
     const double *io_stage[2] = {nullptr, nullptr};
     uint32_t io_ncomp = 0;
     std::vector<uint32_t> chunk_blk, chunk_hub;  // per row chunk: first segment / first hub row (n_chunks+1 entries)
     // graph + work decomposition in HBM
-    uint32_t *d_row_ptr = nullptr, *d_rev = nullptr, *d_nbr = nullptr, *d_src = nullptr;
-    uint32_t *d_deg = nullptr;     // dc 2: degree of every row of the marginal table (own rows, then halo vertices on a shard)
+    device_buffer<uint32_t> d_row_ptr, d_rev, d_nbr, d_src;
+    device_buffer<uint32_t> d_deg;     // dc 2: degree of every row of the marginal table (own rows, then halo vertices on a shard)
     uint64_t n_halo_msgs = 0;      // shards: message records received from peers, kept behind the own records (rev points there)
     int incoming_src = 0;          // shards, reductions: 0 = incoming messages materialised from the marginals, 1 = gathered through rev
-    uint32_t *d_blk_row = nullptr, *d_blk_e0 = nullptr, *d_hub_row = nullptr, *d_hub_blk = nullptr, *d_true = nullptr;
+    device_buffer<uint32_t> d_blk_row, d_blk_e0, d_hub_row, d_hub_blk, d_true;
     // hub rows cut into fragments of BLOCK edges (marginal-gather sweep: k_hub_frag_product / k_hub_frag_cavity)
-    uint32_t *d_frag_hub = nullptr, *d_hub_frag0 = nullptr;
-    double *d_hub_b = nullptr, *d_hub_pA = nullptr;
-    int *d_hub_pE = nullptr;
+    device_buffer<uint32_t> d_frag_hub, d_hub_frag0;
+    device_buffer<double> d_hub_b, d_hub_pA;
+    device_buffer<int> d_hub_pE;
     uint32_t n_frag = 0;
     uint64_t hub_edges = 0;
     std::vector<uint32_t> h_hub_frag0;  // [n_hub + 1]
-    uint32_t *d_fold_counters = nullptr;  // arrival counter of k_fold_finalize (zero between launches)
-    int32_t *d_clamp = nullptr;
-    double *d_prior = nullptr;     // per-vertex prior [N*Q] (sbmbp_set_vertex_prior), or null: none. Belongs to the engine like the graph
+    device_buffer<uint32_t> d_fold_counters;  // arrival counter of k_fold_finalize (zero between launches)
+    device_buffer<int32_t> d_clamp;
+    device_buffer<double> d_prior;  // per-vertex prior [N*Q] (sbmbp_set_vertex_prior), or null: none. Belongs to the engine like the graph
     uint32_t n_blk = 0, n_hub = 0;
     // state in HBM
-    double *d_M[2] = {nullptr, nullptr};
+    // (borrowed: d_psi of a shard is the caller's, sbmbp_shard_desc::psi_buf0/1; d_M, d_psi, d_P and d_prior of a batch's engine
+    // point into the batch's buffers while a replica is bound)
+    device_buffer<double> d_M[2];
     int cur = 0;
-    double *d_psi[2] = {nullptr, nullptr};  // marginals, double buffered (the marginal-gather sweep reads one, writes the other)
+    device_buffer<double> d_psi[2];  // marginals, double buffered (the marginal-gather sweep reads one, writes the other)
     int pcur = 0;
-    dev_params *d_P = nullptr;
-    double *d_partials = nullptr;
-    size_t partials_cap = 0;  // doubles
-    double *d_stage = nullptr;  // first-stage fold output: FOLD_BLOCKS rows
-    double *d_small = nullptr;  // folded results
-    size_t small_cap = 0;
-    double *d_hist = nullptr;
+    device_buffer<dev_params> d_P;
+    device_buffer<double> d_partials;  // grown on demand (ensure_partials)
+    device_buffer<double> d_stage;  // first-stage fold output: FOLD_BLOCKS rows
+    device_buffer<double> d_small;  // folded results, grown on demand
+    device_buffer<double> d_hist;
     uint32_t hist_cap = 0;
-    double *d_mats = nullptr;  // 3 * Q*Q small matrices for the non-edge kernels
+    device_buffer<double> d_mats;  // 3 * Q*Q small matrices for the non-edge kernels
     uint64_t device_bytes = 0;
     // host mirrors
     std::vector<double> cab, W;
@@ -99,8 +115,7 @@ struct sbmbp_engine {
     double beta = 1.0;
     double sum_log_didl = 0.0;  // sum over directed edges of log(d_i d_l) (dc 1 constant of f_site/f_edge)
     bool have_params = false, have_state = false, has_clamp = false, field_fresh = false;
-    void *h_cs = nullptr;            // page-locked: two convergence-state slots for the pipelined batch loop
-    hipEvent_t ev_cs[2] = {nullptr, nullptr};
+    pinned_buffer<conv_state> h_cs;  // two convergence-state slots for the pipelined batch loop (with ev_cs)
     bool init_from_psi = false;  // device initialisation: every message equals its sender's marginal, so the first
                                  // marginal-gather sweep takes the neighbours' marginals as the incoming messages
     bool clamp_onehot = false;  // the clamped rows hold the one-hot state of init flag 1/3: the marginal-gather sweep stays exact
@@ -123,16 +138,19 @@ struct sbmbp_engine {
     int sweep_order = 0;
     bool cs_last = false;  // the last sweeps ran in the coloured order: the field on the device followed them step by step
     uint32_t cs_colours = 0, cs_steps = 0, cs_max_rec = 0;
-    uint64_t cs_bytes = 0;  // HBM of the tables below
     std::vector<uint32_t> cs_seg0, cs_hub0, cs_frag0;  // [cs_steps + 1]: first segment / hub / fragment of every step
-    uint32_t *d_cs_rows = nullptr, *d_cs_loff = nullptr, *d_cs_seg_row0 = nullptr, *d_cs_hub_row = nullptr, *d_cs_hub_rec = nullptr,
-             *d_cs_frag_hub = nullptr, *d_cs_hub_frag0 = nullptr;
+    struct coloured_tables {
+        device_buffer<uint32_t> rows, loff, seg_row0, hub_row, hub_rec, frag_hub, hub_frag0;
+    } cs;
     // stats
     uint64_t sweeps = 0, sweep_launches = 0;
     double sweep_ms = 0.0;
     bool timing = false;
-    std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
+    ~sbmbp_engine() {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+    }
 };
 
 // The current device is a per-thread setting of the HIP runtime: every entry point that takes an engine selects the
@@ -148,33 +166,19 @@ struct device_scope {
 
 namespace {
 
-template <typename T> int dev_alloc(sbmbp_engine *e, T **p, size_t count) {
-    size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    hipError_t r = hipMalloc(reinterpret_cast<void **>(p), bytes);
-    if (r != hipSuccess) {
-        set_error(std::string("hipMalloc(") + std::to_string(bytes) + " B): " + hipGetErrorString(r));
-        return r == hipErrorOutOfMemory ? SBMBP_ERR_NOMEM : SBMBP_ERR_HIP;
-    }
-    e->device_bytes += bytes;
-    return SBMBP_OK;
-}
+// memory of the engine (and of its batch): counted in device_bytes
+template <typename T> int dev_alloc(sbmbp_engine *e, device_buffer<T> &b, size_t count) { return b.alloc(count, &e->device_bytes); }
+int ensure_partials(sbmbp_engine *e, size_t doubles) { return e->d_partials.ensure(doubles, &e->device_bytes); }
+int ensure_small(sbmbp_engine *e, size_t doubles) { return e->d_small.ensure(doubles, &e->device_bytes); }
 
-int ensure_partials(sbmbp_engine *e, size_t doubles) {
-    if (doubles <= e->partials_cap) return SBMBP_OK;
-    if (e->d_partials) { hipFree(e->d_partials); e->device_bytes -= e->partials_cap * 8; }
-    e->partials_cap = 0;
-    CHK(dev_alloc(e, &e->d_partials, doubles));
-    e->partials_cap = doubles;
+// dev_alloc and the copy of n host values behind it on the engine's stream (none when n is 0): complete at the caller's
+// next synchronisation, until which the host array must live
+template <typename T> int dev_upload(sbmbp_engine *e, device_buffer<T> &b, const T *h, size_t n) {
+    CHK(dev_alloc(e, b, n));
+    if (n) HIPCHK(hipMemcpyAsync(b, h, n * sizeof(T), hipMemcpyHostToDevice, e->stream));
     return SBMBP_OK;
 }
-int ensure_small(sbmbp_engine *e, size_t doubles) {
-    if (doubles <= e->small_cap) return SBMBP_OK;
-    if (e->d_small) { hipFree(e->d_small); e->device_bytes -= e->small_cap * 8; }
-    e->small_cap = 0;
-    CHK(dev_alloc(e, &e->d_small, doubles));
-    e->small_cap = doubles;
-    return SBMBP_OK;
-}
+template <typename T> int dev_upload(sbmbp_engine *e, device_buffer<T> &b, const std::vector<T> &h) { return dev_upload(e, b, h.data(), h.size()); }
 
 constexpr uint32_t FOLD_BLOCKS = 256, FOLD_STRIDE_MAX = 128;
 
@@ -285,7 +289,7 @@ struct sweep_bufs {
 };
 sweep_bufs bufs_of_sweep(const sbmbp_engine *e, uint32_t j) {
     const int mc = (e->cur + int(j)) & 1, pc = (e->pcur + int(j)) & 1;
-    return sweep_bufs{pc, e->d_M[mc], e->d_M[mc ^ 1], e->d_psi[pc], e->d_psi[pc ^ 1], e->has_clamp ? e->d_clamp : nullptr};
+    return sweep_bufs{pc, e->d_M[mc], e->d_M[mc ^ 1], e->d_psi[pc], e->d_psi[pc ^ 1], e->has_clamp ? e->d_clamp.get() : nullptr};
 }
 
 int upload_params(sbmbp_engine *e, double crit, bool hinted = false) {
@@ -357,13 +361,11 @@ int setup_hub_frags(sbmbp_engine *e, const std::vector<uint32_t> &hub_row, const
     }
     e->n_frag = uint32_t(frag_hub.size());
     if (!e->n_frag) return SBMBP_OK;
-    CHK(dev_alloc(e, &e->d_frag_hub, frag_hub.size()));
-    CHK(dev_alloc(e, &e->d_hub_frag0, e->h_hub_frag0.size()));
-    CHK(dev_alloc(e, &e->d_hub_b, size_t(e->n_frag) * BLOCK * e->Q));
-    CHK(dev_alloc(e, &e->d_hub_pA, size_t(e->n_frag) * e->Q));
-    CHK(dev_alloc(e, &e->d_hub_pE, size_t(e->n_frag) * e->Q));
-    HIPCHK(hipMemcpyAsync(e->d_frag_hub, frag_hub.data(), frag_hub.size() * 4, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_hub_frag0, e->h_hub_frag0.data(), e->h_hub_frag0.size() * 4, hipMemcpyHostToDevice, e->stream));
+    CHK(dev_upload(e, e->d_frag_hub, frag_hub));
+    CHK(dev_upload(e, e->d_hub_frag0, e->h_hub_frag0));
+    CHK(dev_alloc(e, e->d_hub_b, size_t(e->n_frag) * BLOCK * e->Q));
+    CHK(dev_alloc(e, e->d_hub_pA, size_t(e->n_frag) * e->Q));
+    CHK(dev_alloc(e, e->d_hub_pE, size_t(e->n_frag) * e->Q));
     HIPCHK(hipStreamSynchronize(e->stream));  // frag_hub is a local
     return SBMBP_OK;
 }
@@ -379,40 +381,30 @@ int setup_graph_tables(sbmbp_engine *e, const segment_plan_t &plan, const uint64
     e->h_row_ptr = rp32;
     e->n_blk = uint32_t(plan.blk_row.size() - 1);
     e->n_hub = uint32_t(plan.hub_row.size());
-    CHK(dev_alloc(e, &e->d_row_ptr, rp32.size()));
-    HIPCHK(hipMemcpyAsync(e->d_row_ptr, rp32.data(), rp32.size() * 4, hipMemcpyHostToDevice, e->stream));
-    CHK(dev_alloc(e, &e->d_nbr, e->E2));
-    if (with_rev) CHK(dev_alloc(e, &e->d_rev, e->E2));
-    if (e->E2) {
-        HIPCHK(hipMemcpyAsync(e->d_nbr, nbr, e->E2 * 4, hipMemcpyHostToDevice, e->stream));
-        if (with_rev) HIPCHK(hipMemcpyAsync(e->d_rev, rev, e->E2 * 4, hipMemcpyHostToDevice, e->stream));
-    } else {  // the sweeps' branch-free loads read nbr[0] / rev[0] even when there are no edges
+    CHK(dev_upload(e, e->d_row_ptr, rp32));
+    CHK(dev_upload(e, e->d_nbr, nbr, e->E2));
+    if (with_rev) CHK(dev_upload(e, e->d_rev, rev, e->E2));
+    if (!e->E2) {  // the sweeps' branch-free loads read nbr[0] / rev[0] even when there are no edges
         HIPCHK(hipMemsetAsync(e->d_nbr, 0, 4, e->stream));
         if (with_rev) HIPCHK(hipMemsetAsync(e->d_rev, 0, 4, e->stream));
     }
-    CHK(dev_alloc(e, &e->d_blk_row, plan.blk_row.size()));
-    CHK(dev_alloc(e, &e->d_blk_e0, plan.blk_e0.size()));
-    CHK(dev_alloc(e, &e->d_hub_row, plan.hub_row.size()));
-    CHK(dev_alloc(e, &e->d_hub_blk, plan.hub_blk.size()));
-    HIPCHK(hipMemcpyAsync(e->d_blk_row, plan.blk_row.data(), plan.blk_row.size() * 4, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->d_blk_e0, plan.blk_e0.data(), plan.blk_e0.size() * 4, hipMemcpyHostToDevice, e->stream));
-    if (e->n_hub) {
-        HIPCHK(hipMemcpyAsync(e->d_hub_row, plan.hub_row.data(), plan.hub_row.size() * 4, hipMemcpyHostToDevice, e->stream));
-        HIPCHK(hipMemcpyAsync(e->d_hub_blk, plan.hub_blk.data(), plan.hub_blk.size() * 4, hipMemcpyHostToDevice, e->stream));
-    }
+    CHK(dev_upload(e, e->d_blk_row, plan.blk_row));
+    CHK(dev_upload(e, e->d_blk_e0, plan.blk_e0));
+    CHK(dev_upload(e, e->d_hub_row, plan.hub_row));
+    CHK(dev_upload(e, e->d_hub_blk, plan.hub_blk));
     if (e->n_hub && hub_frags) CHK(setup_hub_frags(e, plan.hub_row, rp32));
-    CHK(dev_alloc(e, &e->d_true, e->N));
-    CHK(dev_alloc(e, &e->d_clamp, e->N));
+    CHK(dev_alloc(e, e->d_true, e->N));
+    CHK(dev_alloc(e, e->d_clamp, e->N));
     HIPCHK(hipMemsetAsync(e->d_true, 0, size_t(e->N) * 4, e->stream));
     HIPCHK(hipMemsetAsync(e->d_clamp, 0xff, size_t(e->N) * 4, e->stream));
-    HIPCHK(hipMemsetAsync(e->d_partials, 0, e->partials_cap * 8, e->stream));
+    HIPCHK(hipMemsetAsync(e->d_partials, 0, e->d_partials.capacity() * 8, e->stream));
     if (e->dc == 1) {  // sum over the directed edges of these rows of log(d_i d_l) = 2 sum_i d_i log d_i (constant of f_site / f_edge)
         double s = 0.0;
         for (uint32_t i = 0; i < e->N; ++i) { const double d = double(rp32[i + 1] - rp32[i]); if (d > 0) s += 2.0 * d * std::log(d); }
         e->sum_log_didl = s;
     }
     if (e->dc == 2) {
-        CHK(dev_alloc(e, &e->d_src, e->E2));
+        CHK(dev_alloc(e, e->d_src, e->E2));
         hipLaunchKernelGGL(k_fill_src, dim3((e->N + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->N, e->d_src);
     }
     HIPCHK(hipStreamSynchronize(e->stream));  // rp32 is a local
@@ -432,17 +424,18 @@ int launch_hub_psi(sbmbp_engine *e, hipStream_t st, uint32_t h0, uint32_t nh, do
     return SBMBP_OK;
 }
 
-// message-gather update of all hub rows: the same two launches over their fragments, incoming messages gathered through rev
+// message-gather update of all hub rows: the same two launches over their fragments, incoming messages gathered through rev.
+// P, partials and prior are the engine's own, or those of one replica of a batch (batch_launch_sweep)
 int launch_hub_msg(sbmbp_engine *e, hipStream_t st, const double *Mold, double *Mnew, const double *psi_old, double *psi_new,
-                   const int32_t *clamp, double damp) {
+                   const int32_t *clamp, double damp, dev_params *P, double *partials, const double *prior) {
     if (!e->n_hub) return SBMBP_OK;
     const uint32_t nf = e->n_frag;
     const hub_frags hf{e->d_frag_hub, e->d_hub_frag0, e->d_hub_b, e->d_hub_pA, e->d_hub_pE};
     DISPATCH_QB(e->Q, e->dc == 2, hipLaunchKernelGGL((k_hub_frag_product_msg<QQ, BB>), dim3(nf), dim3(BLOCK), 0, st, e->d_row_ptr, e->d_rev, e->d_nbr,
-                                                     e->d_deg, Mold, e->d_hub_row, e->d_hub_blk, hf, 0u, e->d_P, e->d_partials, clamp));
+                                                     e->d_deg, Mold, e->d_hub_row, e->d_hub_blk, hf, 0u, P, partials, clamp));
     DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_frag_cavity_msg<QQ>), dim3(nf), dim3(BLOCK), 0, st, e->d_row_ptr, Mold, Mnew, psi_old, psi_new,
-                                        e->d_hub_row, e->d_hub_blk, hf, 0u, e->d_P, int(e->dc != 0), damp,
-                                        e->d_partials, clamp, e->d_prior));
+                                        e->d_hub_row, e->d_hub_blk, hf, 0u, P, int(e->dc != 0), damp,
+                                        partials, clamp, prior));
     return SBMBP_OK;
 }
 
@@ -491,7 +484,7 @@ int launch_sweep(sbmbp_engine *e, uint32_t j, double damp, bool psi_form, bool f
     // grew by exactly the product kernel's 0.037 ms: the fragments cost what their edges cost wherever they run).
     if (e->n_hub) {
         if (psi_form) CHK(launch_hub_psi(e, e->stream, 0, e->n_hub, s.Mnew, s.psi_old, s.psi_new, s.clamp, shard_io{}, s.Mold, int(first_from_psi)));
-        else CHK(launch_hub_msg(e, e->stream, s.Mold, s.Mnew, s.psi_old, s.psi_new, s.clamp, damp));
+        else CHK(launch_hub_msg(e, e->stream, s.Mold, s.Mnew, s.psi_old, s.psi_new, s.clamp, damp, e->d_P, e->d_partials, e->d_prior));
     }
     CHK(timing_begin(e, e->stream, true, &stop));  // around the frame kernel only
     if (psi_form) {
@@ -512,7 +505,7 @@ int launch_sweep(sbmbp_engine *e, uint32_t j, double damp, bool psi_form, bool f
     CHK(timing_end(stop, e->stream));
     // fold of the segment records + K2 in one launch (k_fold_finalize): <= FOLD_BLOCKS workgroups of >= 2048 records each
     if (!e->d_fold_counters) {
-        CHK(dev_alloc(e, &e->d_fold_counters, 1));
+        CHK(dev_alloc(e, e->d_fold_counters, 1));
         HIPCHK(hipMemsetAsync(e->d_fold_counters, 0, 4, e->stream));
     }
     const uint32_t rows = e->n_blk;
@@ -540,11 +533,8 @@ int collect_timing(sbmbp_engine *e) {
     return SBMBP_OK;
 }
 
-struct conv_state { double maxdiff; int conv_iter, sweep_idx, stop, have_prev, hinted, exact, last_exact, pause, ar_fl, ar_gl; };
-static_assert(offsetof(dev_params, ar_gl) - offsetof(dev_params, maxdiff) == offsetof(conv_state, ar_gl), "conv_state mirrors dev_params from maxdiff on");
-
 int read_conv_state(sbmbp_engine *e, conv_state *cs) {
-    HIPCHK(hipMemcpyAsync(cs, reinterpret_cast<const char *>(e->d_P) + offsetof(dev_params, maxdiff), sizeof(conv_state),
+    HIPCHK(hipMemcpyAsync(cs, reinterpret_cast<const char *>(e->d_P.get()) + offsetof(dev_params, maxdiff), sizeof(conv_state),
                           hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return SBMBP_OK;
@@ -554,10 +544,10 @@ int read_conv_state(sbmbp_engine *e, conv_state *cs) {
 // far, wait blocks until that point of the stream and returns it
 int record_conv_state(sbmbp_engine *e, int slot) {
     if (!e->h_cs) {
-        HIPCHK(hipHostMalloc(&e->h_cs, 2 * sizeof(conv_state), hipHostMallocDefault));
+        CHK(e->h_cs.alloc(2));
         for (auto &ev : e->ev_cs) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
-    HIPCHK(hipMemcpyAsync(static_cast<conv_state *>(e->h_cs) + slot, reinterpret_cast<const char *>(e->d_P) + offsetof(dev_params, maxdiff),
+    HIPCHK(hipMemcpyAsync(e->h_cs + slot, reinterpret_cast<const char *>(e->d_P.get()) + offsetof(dev_params, maxdiff),
                           sizeof(conv_state), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipEventRecord(e->ev_cs[slot], e->stream));
     return SBMBP_OK;
@@ -571,7 +561,7 @@ int resume_run(sbmbp_engine *e) {
 }
 int wait_conv_state(sbmbp_engine *e, int slot, conv_state *cs) {
     HIPCHK(hipEventSynchronize(e->ev_cs[slot]));
-    *cs = static_cast<conv_state *>(e->h_cs)[slot];
+    *cs = e->h_cs[slot];
     return SBMBP_OK;
 }
 
@@ -601,12 +591,9 @@ bool psi_form_allowed(const sbmbp_engine *e, double damping) {
 }
 
 void free_coloured(sbmbp_engine *e) {
-    uint32_t **ptrs[] = {&e->d_cs_rows, &e->d_cs_loff, &e->d_cs_seg_row0, &e->d_cs_hub_row, &e->d_cs_hub_rec, &e->d_cs_frag_hub, &e->d_cs_hub_frag0};
-    for (uint32_t **p : ptrs) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    e->cs = sbmbp_engine::coloured_tables();
     e->cs_seg0.clear(); e->cs_hub0.clear(); e->cs_frag0.clear();
     e->cs_colours = e->cs_steps = e->cs_max_rec = 0;
-    e->device_bytes -= e->cs_bytes;
-    e->cs_bytes = 0;
 }
 
 // Device tables of the coloured order from the step of every vertex (host_graph.cpp coloured_plan): the tables are
@@ -616,19 +603,13 @@ int build_coloured(sbmbp_engine *e, const std::vector<uint32_t> &step, uint32_t 
     coloured_tables_t t;
     coloured_step_tables(e->h_row_ptr.data(), e->N, step.data(), n_steps, uint32_t(frame_cap(e->Q)), uint32_t(frame_rcap(e->Q)), uint32_t(BLOCK), t);
     if (t.frag_hub.size() != e->n_frag) { set_error("coloured order: fragment tables disagree"); return SBMBP_ERR_STATE; }
-    auto up = [&](uint32_t **d, const std::vector<uint32_t> &h) -> int {
-        CHK(dev_alloc(e, d, h.size()));
-        e->cs_bytes += std::max<size_t>(h.size(), 1) * 4;
-        if (!h.empty()) HIPCHK(hipMemcpyAsync(*d, h.data(), h.size() * 4, hipMemcpyHostToDevice, e->stream));
-        return SBMBP_OK;
-    };
-    CHK(up(&e->d_cs_rows, t.rows));
-    CHK(up(&e->d_cs_loff, t.loff));
-    CHK(up(&e->d_cs_seg_row0, t.seg_row0));
-    CHK(up(&e->d_cs_hub_row, t.hub_row));
-    CHK(up(&e->d_cs_hub_rec, t.hub_rec));
-    CHK(up(&e->d_cs_frag_hub, t.frag_hub));
-    CHK(up(&e->d_cs_hub_frag0, t.hub_frag0));
+    CHK(dev_upload(e, e->cs.rows, t.rows));
+    CHK(dev_upload(e, e->cs.loff, t.loff));
+    CHK(dev_upload(e, e->cs.seg_row0, t.seg_row0));
+    CHK(dev_upload(e, e->cs.hub_row, t.hub_row));
+    CHK(dev_upload(e, e->cs.hub_rec, t.hub_rec));
+    CHK(dev_upload(e, e->cs.frag_hub, t.frag_hub));
+    CHK(dev_upload(e, e->cs.hub_frag0, t.hub_frag0));
     HIPCHK(hipStreamSynchronize(e->stream));  // the tables are locals
     e->cs_colours = n_colours;
     e->cs_steps = n_steps;
@@ -641,22 +622,22 @@ int build_coloured(sbmbp_engine *e, const std::vector<uint32_t> &step, uint32_t 
 // and k_step_finalize, all in place on the current message buffer and marginal table.
 int launch_coloured_sweep(sbmbp_engine *e, double damp) {
     double *M = e->d_M[e->cur], *psi = e->d_psi[e->pcur];
-    const int32_t *clamp = e->has_clamp ? e->d_clamp : nullptr;
+    const int32_t *clamp = e->has_clamp ? e->d_clamp.get() : nullptr;
     hipEvent_t stop;  // one pair per sweep: the step kernels AND their finalize launches (a sweep is nothing but their sequence)
     CHK(timing_begin(e, e->stream, true, &stop));
-    const hub_frags hf{e->d_cs_frag_hub, e->d_cs_hub_frag0, e->d_hub_b, e->d_hub_pA, e->d_hub_pE};
+    const hub_frags hf{e->cs.frag_hub, e->cs.hub_frag0, e->d_hub_b, e->d_hub_pA, e->d_hub_pE};
     for (uint32_t s = 0; s < e->cs_steps; ++s) {
         const uint32_t seg0 = e->cs_seg0[s], nseg = e->cs_seg0[s + 1] - seg0, nh = e->cs_hub0[s + 1] - e->cs_hub0[s];
         if (nh) {
             const uint32_t f0 = e->cs_frag0[s], nf = e->cs_frag0[s + 1] - f0;
             DISPATCH_QB(e->Q, e->dc == 2, hipLaunchKernelGGL((k_hub_frag_product_msg<QQ, BB>), dim3(nf), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev,
-                                                             e->d_nbr, e->d_deg, M, e->d_cs_hub_row, e->d_cs_hub_rec, hf, f0, e->d_P, e->d_partials, clamp));
-            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_step_cavity<QQ>), dim3(nf), dim3(BLOCK), 0, e->stream, e->d_row_ptr, M, psi, e->d_cs_hub_row,
-                                                e->d_cs_hub_rec, hf, f0, e->d_P, int(e->dc != 0), damp, e->d_partials, clamp));
+                                                             e->d_nbr, e->d_deg, M, e->cs.hub_row, e->cs.hub_rec, hf, f0, e->d_P, e->d_partials, clamp));
+            DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_step_cavity<QQ>), dim3(nf), dim3(BLOCK), 0, e->stream, e->d_row_ptr, M, psi, e->cs.hub_row,
+                                                e->cs.hub_rec, hf, f0, e->d_P, int(e->dc != 0), damp, e->d_partials, clamp));
         }
         if (nseg)
             DISPATCH_QB(e->Q, e->dc == 2, hipLaunchKernelGGL((k_sweep_step<QQ, BB>), dim3(nseg), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev,
-                                                             e->d_nbr, e->d_deg, M, psi, clamp, e->d_cs_rows, e->d_cs_loff, e->d_cs_seg_row0, seg0, e->d_P,
+                                                             e->d_nbr, e->d_deg, M, psi, clamp, e->cs.rows, e->cs.loff, e->cs.seg_row0, seg0, e->d_P,
                                                              int(e->dc != 0), damp, e->d_partials));
         DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_step_finalize<QQ>), dim3(1), dim3(BLOCK), 0, e->stream, e->d_partials, nseg + nh, int(s + 1 == e->cs_steps),
                                             e->d_P, e->d_hist, e->hist_cap));
@@ -801,7 +782,7 @@ int refresh_field(sbmbp_engine *e) {
 int upload_nonedge_mats(sbmbp_engine *e, std::vector<double> &mats, double *wmax_out) {
     mats.assign(3 * e->Q * e->Q, 0.0);
     nonedge_mats(e->Q, e->Nglob, e->cab.data(), e->beta, mats.data(), wmax_out);
-    if (!e->d_mats) CHK(dev_alloc(e, &e->d_mats, mats.size()));
+    if (!e->d_mats) CHK(dev_alloc(e, e->d_mats, mats.size()));
     HIPCHK(hipMemcpyAsync(e->d_mats, mats.data(), mats.size() * 8, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return SBMBP_OK;
@@ -918,7 +899,7 @@ int site_edge_terms(sbmbp_engine *e, bool want_entropy, double out[4], double *d
     }
     CHK(ensure_partials(e, size_t(std::max<uint32_t>(e->n_blk, 1)) * (FE_NP + 1)));
     const double *M = e->d_M[e->cur];
-    const double *Min = (e->sharded && e->incoming_src == 0) ? e->d_Min : nullptr;
+    const double *Min = (e->sharded && e->incoming_src == 0) ? e->d_Min.get() : nullptr;
     const bool dc2 = e->dc == 2;
     const int dcf = int(e->dc != 0);  // (the DC2 variants take 1, the others dc, which is 0 or 1 there)
     if (e->d_prior != nullptr) {  // a per-vertex prior is set: the prior twins, whose site products take the row's prior line
@@ -1047,7 +1028,7 @@ int em_expect(sbmbp_engine *e, double *na_e, double *nna_e, double *cab_e) {
     // k_em_edges reads cab/invN from the parameter block, which is in sync with the host mirror here:
     // sbmbp_set_params uploads, and inside learning the preceding converge uploaded.
     const double *M = e->d_M[e->cur];
-    const double *Min = (e->sharded && e->incoming_src == 0) ? e->d_Min : nullptr;
+    const double *Min = (e->sharded && e->incoming_src == 0) ? e->d_Min.get() : nullptr;
     DISPATCH_QB(Q, e->dc == 2, hipLaunchKernelGGL((k_em_edges<QQ, BB>), dim3(nb), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev,
                                                   e->d_nbr, e->d_deg, e->d_src, M, Min, uint32_t(e->E2), e->d_P, e->d_partials));
     HIPCHK(hipGetLastError());
@@ -1210,7 +1191,8 @@ static int create_engine(sbmbp_engine_t **out, const sbmbp_graph_t *g, uint32_t 
         return SBMBP_ERR_NODEVICE;
     }
     if (device >= 0) HIPCHK(hipSetDevice(device));
-    auto *e = new sbmbp_engine();
+    std::unique_ptr<sbmbp_engine> owner(new sbmbp_engine());
+    sbmbp_engine *e = owner.get();
     HIPCHK(hipGetDevice(&e->device));
     e->N = g->n;
     e->Nglob = g->n;
@@ -1220,38 +1202,33 @@ static int create_engine(sbmbp_engine_t **out, const sbmbp_graph_t *g, uint32_t 
     e->E2 = g->e2();
     HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     e->own_stream = true;
-    const int r = [&]() -> int {
-        segment_plan_t plan;  // one chunk: the shard's decomposition (sbmbp_shard_create) without boundaries inside
-        segment_plan(g->row_ptr.data(), g->n, uint32_t(frame_cap(Q)), uint32_t(frame_rcap(Q)), {}, plan);
-        CHK(ensure_partials(e, (plan.blk_row.size() - 1) * (QMAX + 1)));
-        CHK(setup_graph_tables(e, plan, g->row_ptr.data(), g->nbr.data(), g->rev.data(), true, !e->wide));  // (the wide sweep walks a long row itself)
-        if (own_state) {
-            CHK(dev_alloc(e, &e->d_M[0], std::max<uint64_t>(e->E2, 1) * rec_len(e)));  // records of Q-1 components (Q above 16 labels); >= one record: the sweep's loads are branch-free
-            CHK(dev_alloc(e, &e->d_M[1], std::max<uint64_t>(e->E2, 1) * rec_len(e)));
-            CHK(dev_alloc(e, &e->d_psi[0], size_t(e->N) * Q));
-            CHK(dev_alloc(e, &e->d_psi[1], size_t(e->N) * Q));
-            CHK(dev_alloc(e, &e->d_P, 1));
-        }
-        if (e->wide) CHK(dev_alloc(e, &e->d_Pw, 1));
-        CHK(dev_alloc(e, &e->d_mats, 3 * Q * Q));
-        if (const char *fr = std::getenv("SBMBP_FUSED_REDUCTIONS")) e->fused_reductions = std::atoi(fr);
-        e->hist_cap = 4096;
-        CHK(dev_alloc(e, &e->d_hist, e->hist_cap));
-        CHK(dev_alloc(e, &e->d_fold_counters, 1));
-        HIPCHK(hipMemsetAsync(e->d_fold_counters, 0, 4, e->stream));
-        CHK(ensure_small(e, 8192));
-        CHK(dev_alloc(e, &e->d_stage, size_t(FOLD_BLOCKS) * FOLD_STRIDE_MAX));
-        std::vector<uint32_t> deg(dc == 2 ? e->N : 0);
-        if (dc == 2) {
-            for (uint32_t i = 0; i < g->n; ++i) deg[i] = g->deg(i);
-            CHK(dev_alloc(e, &e->d_deg, e->N));
-            HIPCHK(hipMemcpyAsync(e->d_deg, deg.data(), size_t(e->N) * 4, hipMemcpyHostToDevice, e->stream));
-        }
-        HIPCHK(hipStreamSynchronize(e->stream));  // (deg is a local)
-        return SBMBP_OK;
-    }();
-    if (r != SBMBP_OK) { sbmbp_destroy(e); return r; }
-    *out = e;
+    segment_plan_t plan;  // one chunk: the shard's decomposition (sbmbp_shard_create) without boundaries inside
+    segment_plan(g->row_ptr.data(), g->n, uint32_t(frame_cap(Q)), uint32_t(frame_rcap(Q)), {}, plan);
+    CHK(ensure_partials(e, (plan.blk_row.size() - 1) * (QMAX + 1)));
+    CHK(setup_graph_tables(e, plan, g->row_ptr.data(), g->nbr.data(), g->rev.data(), true, !e->wide));  // (the wide sweep walks a long row itself)
+    if (own_state) {
+        CHK(dev_alloc(e, e->d_M[0], std::max<uint64_t>(e->E2, 1) * rec_len(e)));  // records of Q-1 components (Q above 16 labels); >= one record: the sweep's loads are branch-free
+        CHK(dev_alloc(e, e->d_M[1], std::max<uint64_t>(e->E2, 1) * rec_len(e)));
+        CHK(dev_alloc(e, e->d_psi[0], size_t(e->N) * Q));
+        CHK(dev_alloc(e, e->d_psi[1], size_t(e->N) * Q));
+        CHK(dev_alloc(e, e->d_P, 1));
+    }
+    if (e->wide) CHK(dev_alloc(e, e->d_Pw, 1));
+    CHK(dev_alloc(e, e->d_mats, 3 * Q * Q));
+    if (const char *fr = std::getenv("SBMBP_FUSED_REDUCTIONS")) e->fused_reductions = std::atoi(fr);
+    e->hist_cap = 4096;
+    CHK(dev_alloc(e, e->d_hist, e->hist_cap));
+    CHK(dev_alloc(e, e->d_fold_counters, 1));
+    HIPCHK(hipMemsetAsync(e->d_fold_counters, 0, 4, e->stream));
+    CHK(ensure_small(e, 8192));
+    CHK(dev_alloc(e, e->d_stage, size_t(FOLD_BLOCKS) * FOLD_STRIDE_MAX));
+    std::vector<uint32_t> deg(dc == 2 ? e->N : 0);
+    if (dc == 2) {
+        for (uint32_t i = 0; i < g->n; ++i) deg[i] = g->deg(i);
+        CHK(dev_upload(e, e->d_deg, deg));
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));  // (deg is a local)
+    *out = owner.release();
     return SBMBP_OK;
 }
 
@@ -1260,22 +1237,8 @@ int sbmbp_create(sbmbp_engine_t **out, const sbmbp_graph_t *g, uint32_t Q, uint3
     return create_engine(out, g, Q, dc, device, true);
 }
 
-void sbmbp_destroy(sbmbp_engine_t *e) {
-    if (!e) return;
-    hipSetDevice(e->device);
-    if (e->stream) hipStreamSynchronize(e->stream);
-    if (e->ext_psi) e->d_psi[0] = e->d_psi[1] = nullptr;  // caller-owned
-    void *ptrs[] = {e->d_deg, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_src, e->d_blk_row, e->d_blk_e0, e->d_hub_row, e->d_hub_blk, e->d_true,
-                    e->d_clamp, e->d_M[0], e->d_M[1], e->d_psi[0], e->d_psi[1], e->d_Min, e->d_snd_ptr, e->d_snd_slot, e->d_P, e->d_partials, e->d_small, e->d_hist, e->d_mats,
-                    e->d_stage, e->d_frag_hub, e->d_hub_frag0, e->d_hub_b, e->d_hub_pA, e->d_hub_pE, e->d_fold_counters, e->d_Pw, e->d_prior};
-    for (void *p : ptrs) if (p) hipFree(p);
-    free_coloured(e);
-    for (auto ev : e->ev) hipEventDestroy(ev);
-    if (e->h_cs) (void)hipHostFree(e->h_cs);
-    for (auto ev : e->ev_cs) if (ev) hipEventDestroy(ev);
-    if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
-    delete e;
-}
+// ~sbmbp_engine drains the stream, the buffers go with the members, ~engine_stream destroys the events and the stream
+void sbmbp_destroy(sbmbp_engine_t *e) { delete e; }
 
 int sbmbp_set_stream(sbmbp_engine_t *e, void *hip_stream) {
     device_scope dev_(e);
@@ -1318,50 +1281,36 @@ int sbmbp_init_messages(sbmbp_engine_t *e, uint32_t flag, const int32_t *conf, c
     // the state is generated in slabs of consecutive vertices and each slab is uploaded (marginal rows as they are,
     // messages through the Q -> Q-1 record conversion) while the host already generates the next one
     const uint32_t Q = e->Q;
-    double *tmp = nullptr;
-    uint64_t tmp_cap = 0;
-    hipError_t herr = hipSuccess;
-    double *pin_psi = nullptr, *pin_msg = nullptr;  // page-locked slab buffers: the uploads run at link speed
+    device_buffer<double> tmp;                // the Q-component messages of a slab, grown to the largest slab
+    pinned_buffer<double> pin_psi, pin_msg;  // page-locked slab buffers: the uploads run at link speed
     state_sink sink;
-    sink.alloc = [&](uint64_t np, uint64_t nm, double **pb, double **mb) {
-        if (hipHostMalloc(reinterpret_cast<void **>(&pin_psi), np * 8, hipHostMallocDefault) != hipSuccess) { pin_psi = nullptr; return false; }
-        if (hipHostMalloc(reinterpret_cast<void **>(&pin_msg), nm * 8, hipHostMallocDefault) != hipSuccess) {
-            (void)hipHostFree(pin_psi);
-            pin_psi = pin_msg = nullptr;
-            return false;
-        }
+    sink.alloc = [&](uint64_t np, uint64_t nm, double **pb, double **mb) {  // (false: the generator takes pageable buffers)
+        if (pin_psi.alloc(np) != SBMBP_OK || pin_msg.alloc(nm) != SBMBP_OK) return false;
         *pb = pin_psi;
         *mb = pin_msg;
         return true;
     };
-    sink.put = [&](uint32_t lo, uint32_t hi, const double *prow, const double *mrow) {
-        if (herr != hipSuccess || hi <= lo) return;
-        herr = hipMemcpyAsync(e->d_psi[e->pcur] + size_t(lo) * Q, prow, size_t(hi - lo) * Q * 8, hipMemcpyHostToDevice, e->stream);
+    auto put = [&](uint32_t lo, uint32_t hi, const double *prow, const double *mrow) -> int {
+        HIPCHK(hipMemcpyAsync(e->d_psi[e->pcur] + size_t(lo) * Q, prow, size_t(hi - lo) * Q * 8, hipMemcpyHostToDevice, e->stream));
         const uint64_t k0 = e->h_row_ptr[lo], nm = uint64_t(e->h_row_ptr[hi]) - k0;
-        if (herr == hipSuccess && nm) {
-            if (nm > tmp_cap && !e->wide) {
-                if (tmp) { (void)hipStreamSynchronize(e->stream); (void)hipFree(tmp); tmp = nullptr; }
-                herr = hipMalloc(&tmp, nm * Q * 8);
-                tmp_cap = herr == hipSuccess ? nm : 0;
-            }
-            if (e->wide) {  // full records: straight into the message buffer
-                herr = hipMemcpyAsync(e->d_M[e->cur] + k0 * Q, mrow, nm * Q * 8, hipMemcpyHostToDevice, e->stream);
-            } else {
-            if (herr == hipSuccess) herr = hipMemcpyAsync(tmp, mrow, nm * Q * 8, hipMemcpyHostToDevice, e->stream);
-            if (herr == hipSuccess) {
-                hipLaunchKernelGGL(k_msgs_to_records, dim3(uint32_t((nm + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, e->stream, tmp, nm,
-                                   int(Q), e->d_M[e->cur] + k0 * (Q - 1));
-                herr = hipGetLastError();
-            }
-            }
+        if (nm && e->wide) {  // full records: straight into the message buffer
+            HIPCHK(hipMemcpyAsync(e->d_M[e->cur] + k0 * Q, mrow, nm * Q * 8, hipMemcpyHostToDevice, e->stream));
+        } else if (nm) {
+            CHK(tmp.ensure(nm * Q));  // (nothing in flight reads it: every slab ends with a synchronisation)
+            HIPCHK(hipMemcpyAsync(tmp, mrow, nm * Q * 8, hipMemcpyHostToDevice, e->stream));
+            hipLaunchKernelGGL(k_msgs_to_records, dim3(uint32_t((nm + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, e->stream, tmp.get(), nm,
+                               int(Q), e->d_M[e->cur] + k0 * (Q - 1));
+            HIPCHK(hipGetLastError());
         }
-        if (herr == hipSuccess) herr = hipStreamSynchronize(e->stream);  // the slab buffers are reused by the next slab
+        HIPCHK(hipStreamSynchronize(e->stream));  // the slab buffers are reused by the next slab
+        return SBMBP_OK;
+    };
+    int put_rc = SBMBP_OK;  // the first failure: the slabs behind it are dropped
+    sink.put = [&](uint32_t lo, uint32_t hi, const double *prow, const double *mrow) {
+        if (put_rc == SBMBP_OK && hi > lo) put_rc = put(lo, hi, prow, mrow);
     };
     init_state_host(e->N, e->h_row_ptr.data(), e->E2, Q, flag, conf, seed, nullptr, nullptr, &sink);
-    if (tmp) (void)hipFree(tmp);
-    if (pin_psi) (void)hipHostFree(pin_psi);
-    if (pin_msg) (void)hipHostFree(pin_msg);
-    HIPCHK(herr);
+    CHK(put_rc);
     // a sharded engine takes the declared state as (psi^0, m^-1): sweep 0 reads the buffer it then overwrites
     if (e->E2 && e->sharded)
         HIPCHK(hipMemcpyAsync(e->d_M[e->cur ^ 1], e->d_M[e->cur], e->E2 * (Q - 1) * 8, hipMemcpyDeviceToDevice, e->stream));
@@ -1435,21 +1384,16 @@ static int upload_messages(sbmbp_engine *e, const double *msg_out, double *dst) 
         return SBMBP_OK;
     }
     const uint64_t slab = std::min<uint64_t>(e->E2, STATE_SLAB);
-    double *tmp = nullptr;
-    HIPCHK(hipMalloc(&tmp, slab * e->Q * 8));
+    device_buffer<double> tmp;
+    CHK(tmp.alloc(slab * e->Q));
     for (uint64_t k0 = 0; k0 < e->E2; k0 += slab) {
         const uint64_t n = std::min(slab, e->E2 - k0);
-        hipError_t err = hipMemcpyAsync(tmp, msg_out + k0 * e->Q, n * e->Q * 8, hipMemcpyHostToDevice, e->stream);
-        if (err == hipSuccess) {
-            hipLaunchKernelGGL(k_msgs_to_records, dim3(uint32_t((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, e->stream, tmp, n,
-                               int(e->Q), dst + k0 * (e->Q - 1));
-            err = hipGetLastError();
-        }
-        if (err != hipSuccess) { (void)hipFree(tmp); HIPCHK(err); }
+        HIPCHK(hipMemcpyAsync(tmp, msg_out + k0 * e->Q, n * e->Q * 8, hipMemcpyHostToDevice, e->stream));
+        hipLaunchKernelGGL(k_msgs_to_records, dim3(uint32_t((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, e->stream, tmp.get(), n,
+                           int(e->Q), dst + k0 * (e->Q - 1));
+        HIPCHK(hipGetLastError());
     }
-    hipError_t err = hipStreamSynchronize(e->stream);
-    (void)hipFree(tmp);
-    HIPCHK(err);
+    HIPCHK(hipStreamSynchronize(e->stream));
     return SBMBP_OK;
 }
 
@@ -1460,18 +1404,16 @@ static int download_messages(sbmbp_engine *e, const double *src, double *msg_out
         return SBMBP_OK;
     }
     const uint64_t slab = std::min<uint64_t>(e->E2, STATE_SLAB);
-    double *tmp = nullptr;
-    HIPCHK(hipMalloc(&tmp, slab * e->Q * 8));
+    device_buffer<double> tmp;
+    CHK(tmp.alloc(slab * e->Q));
     for (uint64_t k0 = 0; k0 < e->E2; k0 += slab) {
         const uint64_t n = std::min(slab, e->E2 - k0);
         hipLaunchKernelGGL(k_records_to_msgs, dim3(uint32_t((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, e->stream, src + k0 * (e->Q - 1), n,
-                           int(e->Q), tmp);
-        hipError_t err = hipGetLastError();
-        if (err == hipSuccess) err = hipMemcpyAsync(msg_out + k0 * e->Q, tmp, n * e->Q * 8, hipMemcpyDeviceToHost, e->stream);
-        if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-        if (err != hipSuccess) { (void)hipFree(tmp); HIPCHK(err); }
+                           int(e->Q), tmp.get());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(msg_out + k0 * e->Q, tmp, n * e->Q * 8, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
     }
-    (void)hipFree(tmp);
     return SBMBP_OK;
 }
 
@@ -1513,9 +1455,7 @@ int sbmbp_set_vertex_prior(sbmbp_engine_t *e, const double *prior) {
     if (prior == nullptr) {  // remove
         if (e->d_prior) {
             HIPCHK(hipStreamSynchronize(e->stream));
-            (void)hipFree(e->d_prior);
-            e->d_prior = nullptr;
-            e->device_bytes -= size_t(e->N) * e->Q * 8;
+            e->d_prior.reset();
             e->psi_consistent = false; e->fz.valid = false;
         }
         return SBMBP_OK;
@@ -1526,7 +1466,7 @@ int sbmbp_set_vertex_prior(sbmbp_engine_t *e, const double *prior) {
     std::string why;
     const uint32_t bad = first_bad_prior_row(prior, e->N, e->Q, &why);
     if (bad < e->N) { set_error("sbmbp_set_vertex_prior: prior row of vertex " + std::to_string(bad) + ": " + why); return SBMBP_ERR_ARG; }
-    if (!e->d_prior) CHK(dev_alloc(e, &e->d_prior, size_t(e->N) * e->Q));
+    if (!e->d_prior) CHK(dev_alloc(e, e->d_prior, size_t(e->N) * e->Q));
     HIPCHK(hipMemcpyAsync(e->d_prior, prior, size_t(e->N) * e->Q * 8, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     e->psi_consistent = false; e->fz.valid = false;
@@ -1563,7 +1503,7 @@ int sbmbp_get_field(sbmbp_engine_t *e, double *h) {
     if (!(e->cs_last && e->field_fresh)) CHK(refresh_field(e));
     if (e->wide) {
         std::vector<double> hn(e->Q);
-        HIPCHK(hipMemcpyAsync(hn.data(), reinterpret_cast<const char *>(e->d_Pw) + offsetof(dev_wide, hN), size_t(e->Q) * 8, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(hn.data(), reinterpret_cast<const char *>(e->d_Pw.get()) + offsetof(dev_wide, hN), size_t(e->Q) * 8, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
         for (uint32_t q = 0; q < e->Q; ++q) h[q] = hn[q] * double(e->N);
         return SBMBP_OK;
@@ -1828,10 +1768,10 @@ int sbmbp_shard_create(sbmbp_engine_t **out, const sbmbp_shard_desc *d, uint32_t
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("no HIP device visible; the engine has no CPU fallback"); return SBMBP_ERR_NODEVICE; }
     if (device >= 0) HIPCHK(hipSetDevice(device));
-    auto *e = new sbmbp_engine();
+    std::unique_ptr<sbmbp_engine> owner(new sbmbp_engine());
+    sbmbp_engine *e = owner.get();
     HIPCHK(hipGetDevice(&e->device));
     e->sharded = true;
-    e->ext_psi = true;
     e->N = d->n_own;
     e->Nglob = d->n_global;
     e->n_halo = d->n_halo;
@@ -1840,54 +1780,46 @@ int sbmbp_shard_create(sbmbp_engine_t **out, const sbmbp_shard_desc *d, uint32_t
     e->Q = Q;
     e->dc = dc;
     e->E2 = d->n_edges;
-    e->d_psi[0] = static_cast<double *>(d->psi_buf0);
-    e->d_psi[1] = static_cast<double *>(d->psi_buf1);
-    e->d_red = static_cast<double *>(d->red_buf);
+    e->d_psi[0].borrow(static_cast<double *>(d->psi_buf0));  // the three are the caller's, and stay the caller's
+    e->d_psi[1].borrow(static_cast<double *>(d->psi_buf1));
+    e->d_red.borrow(static_cast<double *>(d->red_buf));
     e->n_halo_msgs = d->n_halo_msgs;
     HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     e->own_stream = true;
     std::vector<uint32_t> chunk_row;  // segments never straddle a chunk boundary
     if (d->n_chunks > 1 && d->chunk_row) chunk_row.assign(d->chunk_row, d->chunk_row + d->n_chunks + 1);
     else chunk_row = {0u, d->n_own};
-    if (chunk_row.front() != 0 || chunk_row.back() != d->n_own) { delete e; set_error("chunk_row must span [0, n_own]"); return SBMBP_ERR_ARG; }
+    if (chunk_row.front() != 0 || chunk_row.back() != d->n_own) { set_error("chunk_row must span [0, n_own]"); return SBMBP_ERR_ARG; }
     for (size_t c = 1; c < chunk_row.size(); ++c)
-        if (chunk_row[c] < chunk_row[c - 1]) { delete e; set_error("chunk_row not monotone"); return SBMBP_ERR_ARG; }
+        if (chunk_row[c] < chunk_row[c - 1]) { set_error("chunk_row not monotone"); return SBMBP_ERR_ARG; }
     for (uint32_t i = 0; i < d->n_own; ++i)
         if (d->row_ptr[i + 1] < d->row_ptr[i]) {
             set_error("shard row_ptr not monotone at local row " + std::to_string(i) + " of " + std::to_string(d->n_own) + ": " +
                       std::to_string(d->row_ptr[i]) + " then " + std::to_string(d->row_ptr[i + 1]) + " (n_edges " + std::to_string(d->n_edges) + ")");
-            delete e;
             return SBMBP_ERR_ARG;
         }
-    const int r = [&]() -> int {
-        segment_plan_t plan;
-        segment_plan(d->row_ptr, d->n_own, uint32_t(frame_cap(Q)), uint32_t(frame_rcap(Q)), chunk_row, plan);
-        e->chunk_blk = plan.chunk_blk;
-        e->chunk_hub = plan.chunk_hub;
-        CHK(ensure_partials(e, std::max<size_t>(plan.blk_row.size() - 1, 64) * (QMAX + 1)));
-        CHK(setup_graph_tables(e, plan, d->row_ptr, d->nbr_local, d->rev_local, d->rev_local != nullptr, true));
-        // records of Q-1 components; >= one record: the sweep's loads are branch-free. With a reverse index the records received
-        // from the peers (the incoming messages of the cut edges) live behind the own ones, so rev addresses one array.
-        CHK(dev_alloc(e, &e->d_M[0], std::max<uint64_t>(e->E2 + e->n_halo_msgs, 1) * (Q - 1)));
-        CHK(dev_alloc(e, &e->d_M[1], std::max<uint64_t>(e->E2 + e->n_halo_msgs, 1) * (Q - 1)));
-        CHK(dev_alloc(e, &e->d_P, 1));
-        e->hist_cap = 4096;
-        CHK(dev_alloc(e, &e->d_hist, e->hist_cap));
-        if (dc == 2) {
-            CHK(dev_alloc(e, &e->d_deg, size_t(d->n_own) + d->n_halo));
-            HIPCHK(hipMemcpyAsync(e->d_deg, d->table_deg, (size_t(d->n_own) + d->n_halo) * 4, hipMemcpyHostToDevice, e->stream));
-        }
-        if (e->n_halo_msgs) {  // defined content before the first exchange
-            HIPCHK(hipMemsetAsync(e->d_M[0] + e->E2 * (Q - 1), 0, e->n_halo_msgs * (Q - 1) * 8, e->stream));
-            HIPCHK(hipMemsetAsync(e->d_M[1] + e->E2 * (Q - 1), 0, e->n_halo_msgs * (Q - 1) * 8, e->stream));
-        }
-        CHK(ensure_small(e, 8192));
-        CHK(dev_alloc(e, &e->d_stage, size_t(FOLD_BLOCKS) * FOLD_STRIDE_MAX));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        return SBMBP_OK;
-    }();
-    if (r != SBMBP_OK) { sbmbp_destroy(e); return r; }
-    *out = e;
+    segment_plan_t plan;
+    segment_plan(d->row_ptr, d->n_own, uint32_t(frame_cap(Q)), uint32_t(frame_rcap(Q)), chunk_row, plan);
+    e->chunk_blk = plan.chunk_blk;
+    e->chunk_hub = plan.chunk_hub;
+    CHK(ensure_partials(e, std::max<size_t>(plan.blk_row.size() - 1, 64) * (QMAX + 1)));
+    CHK(setup_graph_tables(e, plan, d->row_ptr, d->nbr_local, d->rev_local, d->rev_local != nullptr, true));
+    // records of Q-1 components; >= one record: the sweep's loads are branch-free. With a reverse index the records received
+    // from the peers (the incoming messages of the cut edges) live behind the own ones, so rev addresses one array.
+    CHK(dev_alloc(e, e->d_M[0], std::max<uint64_t>(e->E2 + e->n_halo_msgs, 1) * (Q - 1)));
+    CHK(dev_alloc(e, e->d_M[1], std::max<uint64_t>(e->E2 + e->n_halo_msgs, 1) * (Q - 1)));
+    CHK(dev_alloc(e, e->d_P, 1));
+    e->hist_cap = 4096;
+    CHK(dev_alloc(e, e->d_hist, e->hist_cap));
+    if (dc == 2) CHK(dev_upload(e, e->d_deg, d->table_deg, size_t(d->n_own) + d->n_halo));
+    if (e->n_halo_msgs) {  // defined content before the first exchange
+        HIPCHK(hipMemsetAsync(e->d_M[0] + e->E2 * (Q - 1), 0, e->n_halo_msgs * (Q - 1) * 8, e->stream));
+        HIPCHK(hipMemsetAsync(e->d_M[1] + e->E2 * (Q - 1), 0, e->n_halo_msgs * (Q - 1) * 8, e->stream));
+    }
+    CHK(ensure_small(e, 8192));
+    CHK(dev_alloc(e, e->d_stage, size_t(FOLD_BLOCKS) * FOLD_STRIDE_MAX));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    *out = owner.release();
     return SBMBP_OK;
 }
 
@@ -1955,7 +1887,7 @@ int sbmbp_shard_sweep_explicit(sbmbp_engine_t *e, uint32_t j, double damping) {
                     hipLaunchKernelGGL((k_sweep<QQ, BB>), dim3(e->n_blk), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg,
                                        s.Mold, s.Mnew, s.psi_old, s.psi_new, s.clamp, e->d_blk_row, e->d_blk_e0, e->d_P, int(e->dc != 0), damping, e->d_partials));
     CHK(timing_end(stop, e->stream));
-    CHK(launch_hub_msg(e, e->stream, s.Mold, s.Mnew, s.psi_old, s.psi_new, s.clamp, damping));
+    CHK(launch_hub_msg(e, e->stream, s.Mold, s.Mnew, s.psi_old, s.psi_new, s.clamp, damping, e->d_P, e->d_partials, e->d_prior));
     HIPCHK(hipGetLastError());
     return SBMBP_OK;
 }
@@ -2006,12 +1938,8 @@ int sbmbp_shard_set_io(sbmbp_engine_t *e, const uint32_t *snd_ptr, const uint32_
     if (!snd_ptr || (ncomp != e->Q && ncomp + 1 != e->Q)) return arg_error(__func__, __LINE__);
     const uint32_t n_slots = snd_ptr[e->N];
     if ((n_slots && (!snd_slot || !d_sendbuf)) || (e->n_halo && (!d_stage0 || !d_stage1))) return arg_error(__func__, __LINE__);
-    if (e->d_snd_ptr) { hipFree(e->d_snd_ptr); e->d_snd_ptr = nullptr; }
-    if (e->d_snd_slot) { hipFree(e->d_snd_slot); e->d_snd_slot = nullptr; }
-    CHK(dev_alloc(e, &e->d_snd_ptr, size_t(e->N) + 1));
-    CHK(dev_alloc(e, &e->d_snd_slot, std::max<size_t>(1, n_slots)));
-    HIPCHK(hipMemcpyAsync(e->d_snd_ptr, snd_ptr, (size_t(e->N) + 1) * 4, hipMemcpyHostToDevice, e->stream));
-    if (n_slots) HIPCHK(hipMemcpyAsync(e->d_snd_slot, snd_slot, size_t(n_slots) * 4, hipMemcpyHostToDevice, e->stream));
+    CHK(dev_upload(e, e->d_snd_ptr, snd_ptr, size_t(e->N) + 1));  // (tables of an earlier call are released, and leave device_bytes, here)
+    CHK(dev_upload(e, e->d_snd_slot, snd_slot, size_t(n_slots)));
     HIPCHK(hipStreamSynchronize(e->stream));
     e->io_sendbuf = d_sendbuf;
     e->io_stage[0] = d_stage0;
@@ -2191,7 +2119,7 @@ int sbmbp_shard_commit(sbmbp_engine_t *e, uint32_t executed) {
 // ---- reductions on shards: partial -> (caller all-reduces red) -> finish ----------------------------
 static int shard_materialize(sbmbp_engine_t *e) {
     if (e->incoming_src == 1) return SBMBP_OK;  // the reductions gather the incoming messages through rev (halo records in place)
-    if (!e->d_Min) CHK(dev_alloc(e, &e->d_Min, e->E2 * (e->Q - 1)));
+    if (!e->d_Min) CHK(dev_alloc(e, e->d_Min, e->E2 * (e->Q - 1)));
     if (e->E2 == 0) return SBMBP_OK;
     const uint32_t nb = uint32_t(std::min<uint64_t>(4096, (e->E2 + BLOCK - 1) / BLOCK));
     DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_materialize_in<QQ>), dim3(nb), dim3(BLOCK), 0, e->stream, e->d_nbr, e->d_M[e->cur ^ 1],
@@ -2295,7 +2223,7 @@ int sbmbp_shard_em_partial(sbmbp_engine_t *e, uint32_t *n_values) {
     CHK(sbmbp_shard_rowsums_partial(e));
     const uint32_t nb = uint32_t(std::min<uint64_t>(2048, std::max<uint64_t>(1, (e->E2 + BLOCK - 1) / BLOCK)));
     CHK(ensure_partials(e, size_t(nb) * (T + 1)));
-    const double *Min = e->incoming_src == 0 ? e->d_Min : nullptr;
+    const double *Min = e->incoming_src == 0 ? e->d_Min.get() : nullptr;
     DISPATCH_QB(Q, e->dc == 2, hipLaunchKernelGGL((k_em_edges<QQ, BB>), dim3(nb), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev, e->d_nbr, e->d_deg,
                                                   e->d_src, e->d_M[e->cur], Min, uint32_t(e->E2), e->d_P, e->d_partials));
     HIPCHK(hipGetLastError());
@@ -2336,42 +2264,53 @@ struct batch_replica {
     int par = 0;                // which of the two buffers holds the current state
     int ar_fl = 0, ar_gl = -1;  // levels the last converge call ended on
     int prior_state = 0;        // per-vertex prior (sbmbp_batch_set_vertex_prior): 0 = none, 1 = the batch's shared table, 2 = own
-    double *d_prior = nullptr;  // the own table [N*Q] (state 2)
+    device_buffer<double> d_prior;  // the own table [N*Q] (state 2)
     bool cs_last = false;       // the replica's last sweeps ran in the coloured order (sbmbp_engine::cs_last, per replica)
 };
-struct sbmbp_batch {
+// The batch's engine and events, as a base of the batch: the buffers are members of sbmbp_batch and are counted in the engine's
+// device_bytes, so they are released after ~sbmbp_batch has drained the stream and before the engine goes here.
+struct batch_engine {
     sbmbp_engine *e = nullptr;
+    hipEvent_t ev_cs[2] = {nullptr, nullptr};
+    ~batch_engine() {
+        for (auto ev : ev_cs) if (ev) (void)hipEventDestroy(ev);
+        sbmbp_destroy(e);
+    }
+};
+struct sbmbp_batch : batch_engine {
     uint32_t R = 0;
-    double *d_M = nullptr, *d_psi = nullptr, *d_rec = nullptr;
-    dev_params *d_P = nullptr;
-    int *d_par = nullptr;
-    uint32_t *d_cs = nullptr;  // [R] convergence states, gathered (k_batch_conv_states)
+    device_buffer<double> d_M, d_psi, d_rec;
+    device_buffer<dev_params> d_P;
+    device_buffer<int> d_par;
+    device_buffer<uint32_t> d_cs;  // [R] convergence states, gathered (k_batch_conv_states)
     size_t msg_stride = 0, psi_stride = 0, rec_stride = 0;  // doubles per replica
     std::vector<batch_replica> rep;
     std::vector<int> call_par;  // parities at the start of the running call
-    void *h_cs = nullptr;       // page-locked: two slots of R convergence states
-    hipEvent_t ev_cs[2] = {nullptr, nullptr};
+    pinned_buffer<conv_state> h_cs;  // two slots of R convergence states (with ev_cs)
     uint64_t sweeps = 0;
     // batched reductions of an EM step (batch_reductions): inputs [R][3 Q Q] matrices, then parities / mask / refresh mask
-    // as ints; partial tables; one result row per replica. The host sides are page-locked.
-    double *d_em_in = nullptr, *d_em_part[3] = {nullptr, nullptr, nullptr}, *d_em_res = nullptr;
-    size_t em_part_cap[3] = {0, 0, 0}, em_res_cap = 0;
-    void *h_em_in = nullptr, *h_em_res = nullptr;
-    size_t h_em_res_cap = 0;
+    // as ints; partial tables; one result row per replica. The partial and result tables grow on demand.
+    device_buffer<double> d_em_in, d_em_part[3], d_em_res;
+    pinned_buffer<char> h_em_in;
+    pinned_buffer<double> h_em_res;
     // per-vertex priors: the ONE table of the shared replicas, the table of ones that replicas without a table read while
     // another replica holds one (allocated on first need), and per replica the table it reads (device, [R]; what
     // k_sweep_batch_prior and k_em_frame_batch_prior index with blockIdx.y). n_prior = replicas that hold a table: while it is
     // 0 the batch launches what it launches without this feature.
-    double *d_prior_shared = nullptr, *d_prior_ones = nullptr;
-    const double **d_prior_tab = nullptr;
+    device_buffer<double> d_prior_shared, d_prior_ones;
+    device_buffer<const double *> d_prior_tab;
     uint32_t n_prior = 0;
     // agreement of replicas (sbmbp_batch_agreement), all allocated on first need: the slots of the listed replicas, the
     // partial tables of k_agree (grown like the EM partials), the folded n n Q Q results, and the page-locked host side
-    // (AG_MAXN slots, then the results). Capacities in bytes; not counted in device_bytes: the call leaves every statistic alone
-    uint32_t *d_ag_slot = nullptr;
-    double *d_ag_part = nullptr, *d_ag_res = nullptr;
-    size_t ag_slot_cap = 0, ag_part_cap = 0, ag_res_cap = 0, h_ag_cap = 0;
-    void *h_ag = nullptr;
+    // (AG_MAXN slots, then the results). Not counted in device_bytes: the call leaves every statistic alone
+    device_buffer<uint32_t> d_ag_slot;
+    device_buffer<double> d_ag_part, d_ag_res;
+    pinned_buffer<char> h_ag;
+    ~sbmbp_batch() {
+        if (!e) return;
+        (void)hipSetDevice(e->device);
+        if (e->stream) (void)hipStreamSynchronize(e->stream);
+    }
 };
 
 namespace {
@@ -2380,7 +2319,7 @@ namespace {
 const double *batch_prior_of(const sbmbp_batch *b, uint32_t r) {
     if (!b->n_prior) return nullptr;
     const batch_replica &p = b->rep[r];
-    return p.prior_state == 2 ? p.d_prior : (p.prior_state == 1 ? b->d_prior_shared : b->d_prior_ones);
+    return p.prior_state == 2 ? p.d_prior.get() : (p.prior_state == 1 ? b->d_prior_shared.get() : b->d_prior_ones.get());
 }
 
 // binds the batch's engine to replica r for the lifetime of the object
@@ -2391,11 +2330,11 @@ struct bound_replica {
         sbmbp_engine *e = b->e;
         batch_replica &p = b->rep[r];
         for (int k = 0; k < 2; ++k) {
-            e->d_M[k] = b->d_M + (size_t(k) * b->R + r) * b->msg_stride;
-            e->d_psi[k] = b->d_psi + (size_t(k) * b->R + r) * b->psi_stride;
+            e->d_M[k].borrow(b->d_M + (size_t(k) * b->R + r) * b->msg_stride);
+            e->d_psi[k].borrow(b->d_psi + (size_t(k) * b->R + r) * b->psi_stride);
         }
-        e->d_P = b->d_P + r;
-        e->d_prior = const_cast<double *>(batch_prior_of(b, r));  // the reductions and hub launches of the bound engine take the prior kernels
+        e->d_P.borrow(b->d_P + r);
+        e->d_prior.borrow(const_cast<double *>(batch_prior_of(b, r)));  // the reductions and hub launches of the bound engine take the prior kernels
         e->cur = e->pcur = p.par;
         e->cab = p.cab; e->eta = p.eta; e->na = p.na; e->beta = p.beta;
         e->have_params = p.have_params; e->have_state = p.have_state; e->field_fresh = p.field_fresh; e->w_positive = p.w_positive;
@@ -2409,9 +2348,9 @@ struct bound_replica {
         p.cab = e->cab; p.eta = e->eta; p.na = e->na; p.beta = e->beta;
         p.have_params = e->have_params; p.have_state = e->have_state; p.field_fresh = e->field_fresh; p.w_positive = e->w_positive;
         p.par = e->cur;
-        e->d_M[0] = e->d_M[1] = e->d_psi[0] = e->d_psi[1] = nullptr;
-        e->d_P = nullptr;
-        e->d_prior = nullptr;  // the tables are the batch's
+        for (int k = 0; k < 2; ++k) { e->d_M[k].reset(); e->d_psi[k].reset(); }  // unbound: the engine holds no state, and no prior
+        e->d_P.reset();
+        e->d_prior.reset();
         e->cs_last = false;
         e->have_state = e->have_params = false;
     }
@@ -2433,22 +2372,14 @@ int batch_replica_arg(const sbmbp_batch *b, int64_t replica) {
 // pointers), ONE frame launch, ONE fold + update launch
 int batch_launch_sweep(sbmbp_batch *b, const batch_view &bv, uint32_t j, double damp) {
     sbmbp_engine *e = b->e;
-    const int32_t *clamp = e->has_clamp ? e->d_clamp : nullptr;
+    const int32_t *clamp = e->has_clamp ? e->d_clamp.get() : nullptr;
     if (e->n_hub) {
-        double *keep = e->d_partials;
-        int r_ = SBMBP_OK;
-        for (uint32_t r = 0; r < b->R && r_ == SBMBP_OK; ++r) {
+        for (uint32_t r = 0; r < b->R; ++r) {
             const int mc = (b->call_par[r] + int(j)) & 1;
-            e->d_P = b->d_P + r;
-            e->d_prior = const_cast<double *>(batch_prior_of(b, r));
-            e->d_partials = b->d_rec + size_t(r) * b->rec_stride;
-            r_ = launch_hub_msg(e, e->stream, b->d_M + (size_t(mc) * b->R + r) * b->msg_stride, b->d_M + (size_t(mc ^ 1) * b->R + r) * b->msg_stride,
-                                b->d_psi + (size_t(mc) * b->R + r) * b->psi_stride, b->d_psi + (size_t(mc ^ 1) * b->R + r) * b->psi_stride, clamp, damp);
+            CHK(launch_hub_msg(e, e->stream, b->d_M + (size_t(mc) * b->R + r) * b->msg_stride, b->d_M + (size_t(mc ^ 1) * b->R + r) * b->msg_stride,
+                               b->d_psi + (size_t(mc) * b->R + r) * b->psi_stride, b->d_psi + (size_t(mc ^ 1) * b->R + r) * b->psi_stride, clamp, damp,
+                               b->d_P + r, b->d_rec + size_t(r) * b->rec_stride, batch_prior_of(b, r)));
         }
-        e->d_P = nullptr;
-        e->d_prior = nullptr;
-        e->d_partials = keep;
-        CHK(r_);
     }
     const dim3 grid(e->n_blk, b->R);
     if (b->n_prior) {  // a replica holds a per-vertex prior: the prior twin, every replica over the table d_prior_tab names for it
@@ -2471,8 +2402,8 @@ int batch_launch_sweep(sbmbp_batch *b, const batch_view &bv, uint32_t j, double 
 // k_sweep_step_batch and ONE k_step_finalize_batch, all in place on the buffer call_par[r] of every replica.
 int batch_launch_coloured_sweep(sbmbp_batch *b, const batch_view &bv, double damp) {
     sbmbp_engine *e = b->e;
-    const int32_t *clamp = e->has_clamp ? e->d_clamp : nullptr;
-    const hub_frags hf{e->d_cs_frag_hub, e->d_cs_hub_frag0, e->d_hub_b, e->d_hub_pA, e->d_hub_pE};
+    const int32_t *clamp = e->has_clamp ? e->d_clamp.get() : nullptr;
+    const hub_frags hf{e->cs.frag_hub, e->cs.hub_frag0, e->d_hub_b, e->d_hub_pA, e->d_hub_pE};
     for (uint32_t s = 0; s < e->cs_steps; ++s) {
         const uint32_t seg0 = e->cs_seg0[s], nseg = e->cs_seg0[s + 1] - seg0, nh = e->cs_hub0[s + 1] - e->cs_hub0[s];
         if (nh) {
@@ -2481,14 +2412,14 @@ int batch_launch_coloured_sweep(sbmbp_batch *b, const batch_view &bv, double dam
                 double *M = bv.M + (size_t(b->call_par[r]) * b->R + r) * bv.msg_stride, *psi = bv.psi + (size_t(b->call_par[r]) * b->R + r) * bv.psi_stride;
                 double *rec = bv.rec + size_t(r) * bv.rec_stride;
                 DISPATCH_QB(e->Q, e->dc == 2, hipLaunchKernelGGL((k_hub_frag_product_msg<QQ, BB>), dim3(nf), dim3(BLOCK), 0, e->stream, e->d_row_ptr, e->d_rev,
-                                                                 e->d_nbr, e->d_deg, M, e->d_cs_hub_row, e->d_cs_hub_rec, hf, f0, bv.P + r, rec, clamp));
-                DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_step_cavity<QQ>), dim3(nf), dim3(BLOCK), 0, e->stream, e->d_row_ptr, M, psi, e->d_cs_hub_row,
-                                                    e->d_cs_hub_rec, hf, f0, bv.P + r, int(e->dc != 0), damp, rec, clamp));
+                                                                 e->d_nbr, e->d_deg, M, e->cs.hub_row, e->cs.hub_rec, hf, f0, bv.P + r, rec, clamp));
+                DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_hub_step_cavity<QQ>), dim3(nf), dim3(BLOCK), 0, e->stream, e->d_row_ptr, M, psi, e->cs.hub_row,
+                                                    e->cs.hub_rec, hf, f0, bv.P + r, int(e->dc != 0), damp, rec, clamp));
             }
         }
         if (nseg)
             DISPATCH_QB(e->Q, e->dc == 2, hipLaunchKernelGGL((k_sweep_step_batch<QQ, BB>), dim3(nseg, b->R), dim3(frame_cfg<QQ>::TPB), 0, e->stream, e->d_row_ptr,
-                                                             e->d_rev, e->d_nbr, e->d_deg, bv.M, bv.psi, clamp, e->d_cs_rows, e->d_cs_loff, e->d_cs_seg_row0, seg0,
+                                                             e->d_rev, e->d_nbr, e->d_deg, bv.M, bv.psi, clamp, e->cs.rows, e->cs.loff, e->cs.seg_row0, seg0,
                                                              bv.P, bv.par, bv.msg_stride, bv.psi_stride, bv.rec_stride, int(e->dc != 0), damp, bv.rec));
         DISPATCH_Q(e->Q, hipLaunchKernelGGL((k_step_finalize_batch<QQ>), dim3(b->R), dim3(BLOCK), 0, e->stream, bv.P, bv.rec, bv.rec_stride, nseg + nh,
                                             int(s + 1 == e->cs_steps)));
@@ -2534,7 +2465,7 @@ int batch_run(sbmbp_batch *b, const double *crit, const uint8_t *active, uint32_
     HIPCHK(hipMemcpyAsync(b->d_par, b->call_par.data(), size_t(R) * sizeof(int), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     const batch_view bv = view_of(b);
-    conv_state *slots = static_cast<conv_state *>(b->h_cs);
+    conv_state *slots = b->h_cs;
     std::vector<conv_state> cs(R, conv_state{0.0, -1, 0, 0, 0, 0, 0, 1, 0, 0, -1});
     uint32_t done = 0;
     const uint32_t batch_max = std::max<uint32_t>(1, e->check_every);
@@ -2583,35 +2514,6 @@ int batch_run(sbmbp_batch *b, const double *crit, const uint8_t *active, uint32_
     return SBMBP_OK;
 }
 
-void batch_free(sbmbp_batch *b) {
-    if (!b) return;
-    if (b->e) {
-        (void)hipSetDevice(b->e->device);
-        if (b->e->stream) (void)hipStreamSynchronize(b->e->stream);
-        b->e->d_M[0] = b->e->d_M[1] = b->e->d_psi[0] = b->e->d_psi[1] = nullptr;  // they pointed into the batch buffers
-        b->e->d_P = nullptr;
-    }
-    void *ptrs[] = {b->d_M, b->d_psi, b->d_rec, b->d_P, b->d_par, b->d_cs, b->d_em_in, b->d_em_part[0], b->d_em_part[1], b->d_em_part[2], b->d_em_res,
-                    b->d_prior_shared, b->d_prior_ones, b->d_prior_tab, b->d_ag_slot, b->d_ag_part, b->d_ag_res};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    for (batch_replica &p : b->rep) if (p.d_prior) (void)hipFree(p.d_prior);
-    void *hptrs[] = {b->h_cs, b->h_em_in, b->h_em_res, b->h_ag};
-    for (void *p : hptrs) if (p) (void)hipHostFree(p);
-    for (auto ev : b->ev_cs) if (ev) (void)hipEventDestroy(ev);
-    if (b->e) sbmbp_destroy(b->e);
-    delete b;
-}
-
-// device buffer of at least `need` doubles (grown, never shrunk)
-int batch_ensure(sbmbp_batch *b, double **p, size_t *cap, size_t need) {
-    if (need <= *cap) return SBMBP_OK;
-    if (*p) { (void)hipFree(*p); b->e->device_bytes -= *cap * 8; *p = nullptr; }
-    *cap = 0;
-    CHK(dev_alloc(b->e, p, need));
-    *cap = need;
-    return SBMBP_OK;
-}
-
 // The reductions of ONE EM step for every replica of the mask (null = all), from one launch sequence and one copy to the
 // host (kernels_batch.h): field refresh where the field is stale, frame pass (+ k_fe_hub per replica where the graph has
 // hub rows), the numerators' own kernel above EM_FRAME_QMAX labels, all-pairs non-edge term under dc 0 (exact or moment
@@ -2630,11 +2532,10 @@ int batch_reductions(sbmbp_batch *b, const uint8_t *mask, double *na_e, double *
     // ---- host: per-replica matrices, series order, masks -> one upload
     const size_t in_doubles = size_t(R) * 3 * QQ2, in_bytes = in_doubles * 8 + size_t(3) * R * sizeof(int);
     if (!b->h_em_in) {
-        HIPCHK(hipHostMalloc(&b->h_em_in, in_bytes, hipHostMallocDefault));
-        size_t cap = 0;
-        CHK(batch_ensure(b, &b->d_em_in, &cap, in_bytes / 8 + 1));
+        CHK(b->h_em_in.alloc(in_bytes));
+        CHK(dev_alloc(e, b->d_em_in, in_bytes / 8 + 1));
     }
-    double *h_mats = static_cast<double *>(b->h_em_in);
+    double *h_mats = reinterpret_cast<double *>(b->h_em_in.get());
     int *h_par = reinterpret_cast<int *>(h_mats + in_doubles), *h_act = h_par + R, *h_ref = h_act + R;
     const double *d_mats = b->d_em_in;
     const int *d_par = reinterpret_cast<const int *>(b->d_em_in + in_doubles), *d_act = d_par + R, *d_ref = d_act + R;
@@ -2665,19 +2566,14 @@ int batch_reductions(sbmbp_batch *b, const uint8_t *mask, double *na_e, double *
     const size_t part0 = size_t(R) * std::max<size_t>(size_t(rows) * NP, size_t(nbf) * (Q + 1));  // field partials are folded before the frame pass writes
     const size_t part1 = em_in_frame ? 0 : size_t(R) * nbe * T;
     const size_t part2 = !nonedge ? 0 : (exact ? size_t(R) * g * g : size_t(R) * nbm * Tm);
-    CHK(batch_ensure(b, &b->d_em_part[0], &b->em_part_cap[0], part0));
-    if (part1) CHK(batch_ensure(b, &b->d_em_part[1], &b->em_part_cap[1], part1));
-    if (part2) CHK(batch_ensure(b, &b->d_em_part[2], &b->em_part_cap[2], part2));
-    CHK(batch_ensure(b, &b->d_em_res, &b->em_res_cap, size_t(R) * RES));
-    if (b->h_em_res_cap < size_t(R) * RES) {
-        if (b->h_em_res) { (void)hipHostFree(b->h_em_res); b->h_em_res = nullptr; b->h_em_res_cap = 0; }
-        HIPCHK(hipHostMalloc(&b->h_em_res, size_t(R) * RES * 8, hipHostMallocDefault));
-        b->h_em_res_cap = size_t(R) * RES;
-    }
+    const size_t part[3] = {part0, part1, part2};
+    for (int k = 0; k < 3; ++k) CHK(b->d_em_part[k].ensure(part[k], &e->device_bytes));
+    CHK(b->d_em_res.ensure(size_t(R) * RES, &e->device_bytes));
+    CHK(b->h_em_res.ensure(size_t(R) * RES));
 
     // ---- device: one launch sequence for all replicas
     hipStream_t st = e->stream;
-    HIPCHK(hipMemcpyAsync(b->d_em_in, b->h_em_in, in_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(b->d_em_in, b->h_em_in.get(), in_bytes, hipMemcpyHostToDevice, st));
     if (any_refresh) {  // the site terms read h of the current marginals (k_psi_sum + k_finalize mode 2)
         DISPATCH_Q(Q, hipLaunchKernelGGL((k_psi_sum_batch<QQ>), dim3(nbf, R), dim3(BLOCK), 0, st, e->d_row_ptr, b->d_psi, d_par, d_ref, b->psi_stride,
                                          R, N, 4096u, int(e->dc != 0), b->d_em_part[0]));
@@ -2734,7 +2630,7 @@ int batch_reductions(sbmbp_batch *b, const uint8_t *mask, double *na_e, double *
     HIPCHK(hipStreamSynchronize(st));  // the round's one synchronisation
 
     // ---- host: per replica
-    const double *res = static_cast<const double *>(b->h_em_res);
+    const double *res = b->h_em_res;
     std::vector<double> ce(QQ2);
     for (uint32_t r = 0; r < R; ++r) {
         if (!h_act[r]) continue;
@@ -2807,27 +2703,11 @@ int batch_agreement(sbmbp_batch *b, int kind, const uint32_t *list, uint32_t n, 
     const uint32_t gx = uint32_t(std::max<size_t>(1, std::min<size_t>({size_t((n_trips + 3) / 4), size_t(AG_GRID / gy), AG_PART_BUDGET / (size_t(CP) * CP)})));
     const size_t n_res = size_t(nQ) * nQ, h_bytes = size_t(AG_MAXN) * sizeof(uint32_t) + n_res * 8;
     // grown, never shrunk, like the EM partials - but outside device_bytes: the call changes no statistic of the batch
-    auto ensure = [](void **p, size_t *cap, size_t bytes) -> int {
-        if (bytes <= *cap) return SBMBP_OK;
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
-        *cap = 0;
-        const hipError_t r = hipMalloc(p, bytes);
-        if (r != hipSuccess) {
-            set_error(std::string("hipMalloc(") + std::to_string(bytes) + " B): " + hipGetErrorString(r));
-            return r == hipErrorOutOfMemory ? SBMBP_ERR_NOMEM : SBMBP_ERR_HIP;
-        }
-        *cap = bytes;
-        return SBMBP_OK;
-    };
-    CHK(ensure(reinterpret_cast<void **>(&b->d_ag_slot), &b->ag_slot_cap, size_t(AG_MAXN) * sizeof(uint32_t)));
-    CHK(ensure(reinterpret_cast<void **>(&b->d_ag_part), &b->ag_part_cap, size_t(gx) * CP * CP * 8));
-    CHK(ensure(reinterpret_cast<void **>(&b->d_ag_res), &b->ag_res_cap, n_res * 8));
-    if (b->h_ag_cap < h_bytes) {
-        if (b->h_ag) { (void)hipHostFree(b->h_ag); b->h_ag = nullptr; b->h_ag_cap = 0; }
-        HIPCHK(hipHostMalloc(&b->h_ag, h_bytes, hipHostMallocDefault));
-        b->h_ag_cap = h_bytes;
-    }
-    uint32_t *h_slot = static_cast<uint32_t *>(b->h_ag);
+    CHK(b->d_ag_slot.ensure(AG_MAXN));
+    CHK(b->d_ag_part.ensure(size_t(gx) * CP * CP));
+    CHK(b->d_ag_res.ensure(n_res));
+    CHK(b->h_ag.ensure(h_bytes));
+    uint32_t *h_slot = reinterpret_cast<uint32_t *>(b->h_ag.get());
     const double *res = reinterpret_cast<const double *>(h_slot + AG_MAXN);
     for (uint32_t x = 0; x < n; ++x) {
         const uint32_t r = list ? list[x] : x;
@@ -2867,11 +2747,10 @@ int sbmbp_batch_create(sbmbp_batch_t **out, const sbmbp_graph_t *g, uint32_t Q, 
     if (Q < 2) { set_error("Q must be at least 2"); return SBMBP_ERR_ARG; }
     if (dc > 2) { set_error("deg_corr_flag must be 0, 1 or 2"); return SBMBP_ERR_ARG; }
     if (Q > 16) { set_error("replica batches are implemented up to Q = 16 (the lane-per-edge kernels); Q = " + std::to_string(Q)); return SBMBP_ERR_UNSUPPORTED; }
-    sbmbp_engine *e = nullptr;
-    CHK(create_engine(&e, g, Q, dc, device, false));  // the message, marginal and parameter buffers are the batch's
+    std::unique_ptr<sbmbp_batch> b(new sbmbp_batch());
+    CHK(create_engine(&b->e, g, Q, dc, device, false));  // the message, marginal and parameter buffers are the batch's
+    sbmbp_engine *e = b->e;
     device_scope dev_(e);
-    auto *b = new sbmbp_batch();
-    b->e = e;
     b->R = n_replicas;
     e->gather_mode = 1;  // message-gather form only: the reductions of a bound replica take the message-gather kernels too
     b->msg_stride = size_t(std::max<uint64_t>(e->E2, 1)) * (Q - 1);  // >= one record: the sweep's loads are branch-free
@@ -2880,33 +2759,30 @@ int sbmbp_batch_create(sbmbp_batch_t **out, const sbmbp_graph_t *g, uint32_t Q, 
     const uint64_t R = n_replicas;
     const uint64_t need = R * (2 * uint64_t(b->msg_stride) + 2 * uint64_t(b->psi_stride)) * 8;
     size_t free_b = 0, total_b = 0;
-    int r = SBMBP_OK;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b) {
         set_error("a batch of " + std::to_string(R) + " replicas needs " + std::to_string(need) + " B of HBM for its states, " + std::to_string(free_b) + " B are free");
-        r = SBMBP_ERR_NOMEM;
+        return SBMBP_ERR_NOMEM;
     }
-    if (r == SBMBP_OK) r = dev_alloc(e, &b->d_M, 2 * R * b->msg_stride);
-    if (r == SBMBP_OK) r = dev_alloc(e, &b->d_psi, 2 * R * b->psi_stride);
-    if (r == SBMBP_OK) r = dev_alloc(e, &b->d_rec, R * b->rec_stride);
-    if (r == SBMBP_OK) r = dev_alloc(e, &b->d_P, R);
-    if (r == SBMBP_OK) r = dev_alloc(e, &b->d_par, R);
-    if (r == SBMBP_OK) r = dev_alloc(e, &b->d_cs, R * (sizeof(conv_state) / 4));
-    if (r == SBMBP_OK) r = dev_alloc(e, &b->d_prior_tab, R);  // filled when a table is set; never read before
-    hipError_t h = hipSuccess;
-    if (r == SBMBP_OK) h = hipMemsetAsync(b->d_rec, 0, R * b->rec_stride * 8, e->stream);
-    if (r == SBMBP_OK && h == hipSuccess) h = hipMemsetAsync(b->d_P, 0, R * sizeof(dev_params), e->stream);
-    if (r == SBMBP_OK && h == hipSuccess) h = hipMemsetAsync(b->d_par, 0, R * sizeof(int), e->stream);
-    if (r == SBMBP_OK && h == hipSuccess) h = hipHostMalloc(&b->h_cs, 2 * R * sizeof(conv_state), hipHostMallocDefault);
-    for (auto &ev : b->ev_cs) if (r == SBMBP_OK && h == hipSuccess) h = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (r == SBMBP_OK && h == hipSuccess) h = hipStreamSynchronize(e->stream);
-    if (r == SBMBP_OK && h != hipSuccess) { set_error(std::string("sbmbp_batch_create: ") + hipGetErrorString(h)); r = SBMBP_ERR_HIP; }
-    if (r != SBMBP_OK) { batch_free(b); return r; }
+    CHK(dev_alloc(e, b->d_M, 2 * R * b->msg_stride));
+    CHK(dev_alloc(e, b->d_psi, 2 * R * b->psi_stride));
+    CHK(dev_alloc(e, b->d_rec, R * b->rec_stride));
+    CHK(dev_alloc(e, b->d_P, R));
+    CHK(dev_alloc(e, b->d_par, R));
+    CHK(dev_alloc(e, b->d_cs, R * (sizeof(conv_state) / 4)));
+    CHK(dev_alloc(e, b->d_prior_tab, R));  // filled when a table is set; never read before
+    HIPCHK(hipMemsetAsync(b->d_rec, 0, R * b->rec_stride * 8, e->stream));
+    HIPCHK(hipMemsetAsync(b->d_P, 0, R * sizeof(dev_params), e->stream));
+    HIPCHK(hipMemsetAsync(b->d_par, 0, R * sizeof(int), e->stream));
+    CHK(b->h_cs.alloc(2 * R));
+    for (auto &ev : b->ev_cs) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIPCHK(hipStreamSynchronize(e->stream));
     b->rep.resize(n_replicas);
-    *out = b;
+    *out = b.release();
     return SBMBP_OK;
 }
 
-void sbmbp_batch_destroy(sbmbp_batch_t *b) { batch_free(b); }
+// ~sbmbp_batch drains the stream, the buffers go with the members, ~batch_engine destroys the events and the engine
+void sbmbp_batch_destroy(sbmbp_batch_t *b) { delete b; }
 
 uint32_t sbmbp_batch_num_replicas(const sbmbp_batch_t *b) { return b ? b->R : 0; }
 
@@ -2996,31 +2872,28 @@ int sbmbp_batch_set_vertex_prior(sbmbp_batch_t *b, int replica, const double *pr
         shared += next[r] == 1;
     }
     const bool need_ones = held && held < R;
-    auto drop = [&](double **p) {
-        if (*p) { (void)hipFree(*p); *p = nullptr; e->device_bytes -= std::max<size_t>(n, 1) * 8; }
-    };
-    // allocations first: a table that does not fit leaves the batch as it was
-    double **slot = replica == -1 ? &b->d_prior_shared : &b->rep[replica].d_prior;
+    // allocations first, into locals: a table that does not fit leaves the batch as it was
+    device_buffer<double> &slot = replica == -1 ? b->d_prior_shared : b->rep[replica].d_prior;
+    device_buffer<double> new_ones, new_slot;
     const bool fresh_ones = need_ones && !b->d_prior_ones;
-    if (fresh_ones) CHK(dev_alloc(e, &b->d_prior_ones, n));
-    if (prior && !*slot) {
-        const int rc = dev_alloc(e, slot, n);
-        if (rc != SBMBP_OK) { if (fresh_ones) drop(&b->d_prior_ones); return rc; }
-    }
+    if (fresh_ones) CHK(dev_alloc(e, new_ones, n));
+    if (prior && !slot) CHK(dev_alloc(e, new_slot, n));
     HIPCHK(hipStreamSynchronize(e->stream));  // nothing in flight reads a table that is overwritten or freed below
+    if (new_ones) b->d_prior_ones = std::move(new_ones);
+    if (new_slot) slot = std::move(new_slot);
     std::vector<double> ones;
     if (fresh_ones) {
         ones.assign(n, 1.0);
         HIPCHK(hipMemcpyAsync(b->d_prior_ones, ones.data(), n * 8, hipMemcpyHostToDevice, e->stream));
     }
-    if (prior) HIPCHK(hipMemcpyAsync(*slot, prior, n * 8, hipMemcpyHostToDevice, e->stream));
+    if (prior) HIPCHK(hipMemcpyAsync(slot, prior, n * 8, hipMemcpyHostToDevice, e->stream));
     for (uint32_t r = 0; r < R; ++r) {
         batch_replica &p = b->rep[r];
         p.prior_state = next[r];
-        if (next[r] != 2) drop(&p.d_prior);
+        if (next[r] != 2) p.d_prior.reset();
     }
-    if (!shared) drop(&b->d_prior_shared);
-    if (!need_ones) drop(&b->d_prior_ones);
+    if (!shared) b->d_prior_shared.reset();
+    if (!need_ones) b->d_prior_ones.reset();
     b->n_prior = held;
     // (what the batch caches about a replica's state is its field, which no prior enters; the engine's caches, psi_consistent
     // and the fused pass, are dropped whenever a replica is bound)
@@ -3040,7 +2913,7 @@ int sbmbp_batch_get_vertex_prior(sbmbp_batch_t *b, uint32_t replica, double *pri
     if (prior && p.prior_state) {
         sbmbp_engine *e = b->e;
         device_scope dev_(e);
-        HIPCHK(hipMemcpyAsync(prior, p.prior_state == 2 ? p.d_prior : b->d_prior_shared, size_t(e->N) * e->Q * 8, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(prior, p.prior_state == 2 ? p.d_prior.get() : b->d_prior_shared.get(), size_t(e->N) * e->Q * 8, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
     }
     return SBMBP_OK;
@@ -3103,12 +2976,8 @@ int sbmbp_batch_set_sweep_order(sbmbp_batch_t *b, int order, const uint32_t *col
     const size_t need = size_t(std::max<uint32_t>(std::max(e->n_blk, e->cs_max_rec), 1)) * (e->Q + 1);
     if (need > b->rec_stride) {
         HIPCHK(hipStreamSynchronize(e->stream));  // nothing in flight writes the records that are freed
-        double *rec = nullptr;
-        const int r = dev_alloc(e, &rec, size_t(b->R) * need);
+        const int r = b->d_rec.replace(size_t(b->R) * need, &e->device_bytes);  // (a failure leaves the records as they were)
         if (r != SBMBP_OK) { e->sweep_order = 0; return r; }
-        (void)hipFree(b->d_rec);
-        e->device_bytes -= size_t(b->R) * b->rec_stride * 8;
-        b->d_rec = rec;
         b->rec_stride = need;
         HIPCHK(hipMemsetAsync(b->d_rec, 0, size_t(b->R) * need * 8, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
