@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import agreement_model as M
+import batch_scale_graph as sc
 from conftest import ROOT, args_of, golden, gpath
 from test_gpu_batch import batch_from
 
@@ -61,8 +62,14 @@ def check_against_model(b, psis, replicas=None, kinds=KINDS):
     """all kinds against the model on the tables psis (those of the listed replicas). SOFT and HARD_SOFT entrywise to
     4 N 2^-53 C + 1e-300: both sides add N non-negative terms in some order, each within N 2^-53 C of the exact sum. HARD with ==:
     integer sums below 2^53. The overlap is the brute-force maximum for Q <= 8 (its Q terms are added in one order on both sides
-    only up to rounding: Q 2^-53 relative), and always the trace along the returned permutation."""
+    only up to rounding: Q 2^-53 relative), and always the trace along the returned permutation. Above 64 pairs the brute force
+    takes the first 8 x 8 pairs and 64 drawn ones; the trace and the permutation are checked on every pair."""
     N, Q = psis[0].shape
+    n = len(psis)
+    brute = None
+    if n * n > 64:
+        drawn = np.random.default_rng(n * 1000 + Q).integers(0, n, size=(64, 2))
+        brute = {(x, y) for x in range(8) for y in range(8)} | {(int(x), int(y)) for x, y in drawn}
     out = {}
     for kind in kinds:
         ov, C, perm = b.agreement(kind, replicas)
@@ -75,14 +82,13 @@ def check_against_model(b, psis, replicas=None, kinds=KINDS):
             err = np.abs(C - Cm)
             print(kind, "max error / bound", np.nanmax(err / (4 * N * 2.0 ** -53 * np.abs(Cm) + 1e-300)))
             assert (err <= 4 * N * 2.0 ** -53 * np.abs(Cm) + 1e-300).all(), kind
-        n = len(psis)
         for x in range(n):
             for y in range(n):
                 p = perm[x, y]
                 assert sorted(p) == list(range(Q))
                 tr = sum(C[x, y, a, p[a]] for a in range(Q)) / N
                 assert ov[x, y] == tr
-                if Q <= 8:
+                if Q <= 8 and (brute is None or (x, y) in brute):
                     best, _ = M.overlap_brute(C[x, y], N)
                     assert abs(ov[x, y] - best) <= 2 * Q * 2.0 ** -53 * max(best, 1e-300), (kind, x, y, ov[x, y], best)
         out[kind] = (ov, C, perm)
@@ -99,6 +105,42 @@ def test_all_kinds_against_the_model(S, n, Q):
     for x in range(n):  # what the call must read is what get_state returns
         assert np.array_equal(b.get_state(x, msg=False)[0], psis[x])
     check_against_model(b, psis)
+    b.close()
+
+
+@pytest.mark.parametrize("n,Q", sc.AGREE)
+def test_every_tile_shape_against_the_model(S, n, Q):
+    """with the cases above, every tile count CT = ceil(n Q / 16) from 1 to 16 (tests/batch_scale_graph.py agree_plan;
+    tests/test_batch_scale_cpu.py asserts the coverage): the three k_agree<KIND, 4> instantiations (CT 3 and 4), every ragged
+    last workgroup row - (7, 2), (6, 4), (5, 5, 1), (5, 5, 2), (4, 4, 4, 1 .. 3) -, both parities of the image's row stride,
+    exact multiples of 16 columns and one column under and over, and more than 16 replicas: label rows of (n + 7) & ~7 bytes
+    and a slot table filled by more than one wave, up to AG_MAXN = 128 replicas"""
+    N = 777
+    p = sc.agree_plan(n, Q)
+    print("agreement n %d Q %d: CT %d, TPW %d, workgroup rows %s, S %d, LN %d, %d padding columns"
+          % (n, Q, p["CT"], p["TPW"], p["split"], p["S"], p["LN"], p["pad"]))
+    g, b = ring_batch(S, N, Q, n)
+    psis = random_tables(np.random.default_rng(100 * n + Q), n, N, Q)
+    set_tables(b, psis)
+    check_against_model(b, psis)
+    b.close()
+
+
+def test_the_partial_table_budget_decides_the_grid(S):
+    """N = 20 011 with 256 columns: the budget of the partial tables (128 tables of 512 KB) decides the number of workgroups
+    along the vertices, not the trips (157); every workgroup walks four or five trips, and the fold adds 128 tables"""
+    N, n, Q = sc.AGREE_BUDGET
+    p = sc.agree_plan(n, Q)
+    terms = sc.agree_gx_terms(N, p["CP"], p["gy"])
+    assert terms == (157, 256, 128) and sc.agree_gx(N, p["CP"], p["gy"]) == 128
+    g, b = ring_batch(S, N, Q, n)
+    psis = random_tables(np.random.default_rng(20011), n, N, Q)
+    set_tables(b, psis)
+    first = check_against_model(b, psis)
+    for kind in KINDS:
+        again = b.agreement(kind)
+        for u, v in zip(first[kind], again):
+            assert u.tobytes() == v.tobytes(), kind
     b.close()
 
 
